@@ -11,12 +11,24 @@ data: forward + backward over 64 labeled and 128 unlabeled frames per GPU (BASEL
 temporal + pca_singleview + unimodal_mse losses, gradient all-reduce over RCCL when N > 1, fused Adam.  Inputs are
 resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the steps and prints the line: metric, value (frames/s), unit, higher_is_better, dtype,
+ms_per_step, the step's configuration and its memory / communication counts.
+
+    --dump-outputs DIR   after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the loss, the logged
+                         scalars and a fixed, seeded sample of the parameters and gradients after it (--predict: keypoints + confidences).
+                         The inputs are seeded, so two builds can be compared output for output.
+    --full               everything else the benchmark measures (below), in the same run.
+
+Extra objects in the line with --full:
   roofline      MFMA roofline of the convolution kernels (the dominant cost): algorithmic FLOPs / HIP-event time per
                 launch, measured on the launch stream inside the timed steps; by_kernel gives per-symbol averages that
                 the committed rocprofv3 summary (profiles/) must reproduce.
   cpu_baseline  the CPU oracle (oracle/restated.py: the reference's arithmetic restated in torch fp32, pinned against
                 the verbatim reference modules) timed on this host's cores for a bounded sample of the same workload.
+  roofline_hbm  HBM roofline of the heat-map kernels, timed in launches of their own after the steps.
+  secondary     short lines of the other BASELINE.json configurations (256 px, unfrozen backbone, peaked maps, Trainer.fit, ViT-S,
+                multiview, inference, fp32), single-GPU headline shape only.
+  host_enqueue_idle_queue_ms   host cost of one extra step enqueued onto the idle GPU.
 """
 
 from __future__ import annotations
@@ -42,9 +54,53 @@ TRAIN_GFLOP_PER_FRAME = {384: 72.4, 256: 32.2}  # 3 x 2 
 VIT_S_TRAIN_GFLOP_PER_FRAME = {384: 93.1, 256: 36.9}  # SURVEY.md section 8(d), ViT-S/16
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all arrays together
+DUMP_SAMPLE = 1 << 22         # elements kept of a flat buffer larger than this (indices drawn with a fixed seed: the same every run)
+
+
 def _sync(dev) -> None:
     if dev.type == "cuda":
         torch.cuda.synchronize()
+
+
+def _fixed_sample(buf: torch.Tensor, seed: int) -> torch.Tensor:
+    flat = buf.detach().reshape(-1)
+    if flat.numel() <= DUMP_SAMPLE:
+        return flat
+    idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def step_outputs(model, loss: torch.Tensor | None = None) -> dict:
+    """What a caller of the training step receives from its last call: the loss, the logged scalars, and the model it updated (master
+    parameters and gradients of the flat buffers, a fixed sample of them when they are larger than DUMP_SAMPLE)."""
+    import re
+
+    out = {} if loss is None else {"loss": loss.detach().reshape(-1)}
+    for k, v in sorted(getattr(model, "logged", {}).items()):
+        out["logged_" + re.sub(r"[^A-Za-z0-9_.-]", "_", k)] = torch.as_tensor(v).detach().reshape(-1)
+    net = getattr(model, "net", None)
+    for attr, name, seed in (("P", "params", 0), ("G", "grads", 1)):
+        buf = getattr(net, attr, None)
+        if torch.is_tensor(buf):
+            out[name + ("_sample" if buf.numel() > DUMP_SAMPLE else "")] = _fixed_sample(buf, seed)
+    return out
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as <path>/<name>.npy, float64 kept, everything else float32; at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+
+    conv = {}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        conv[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def synth_batch(dev, rank: int, size: int, n_lab: int, n_unlab: int, K: int):
@@ -400,6 +456,8 @@ def predict_bench(args, model, batch, dev, rank: int, world: int) -> dict:
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, {"keypoints": out[0][0], "confidences": out[0][1]})
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -476,6 +534,8 @@ def fit_line(args, dev, rank: int, world: int) -> dict:
     trainer.fit(model, lambda epoch: batches(args.warmup, args.steps))
     _sync(dev)
     elapsed = time.perf_counter() - t0
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(model))
     frames = (args.labeled + args.unlabeled) * args.steps
     rec = trainer.logged_history[-1] if trainer.logged_history else {}
     return {"metric": f"training frames/sec through Trainer.fit + device-side producers, ResNet-50 {size}x{size} {K}-kp semi-sup",
@@ -529,15 +589,19 @@ def train_line(args, dev, rank: int, world: int) -> dict:
         trainer.training_batch(model, batch, i)
     _sync(dev)
     barrier()
-    # Per-launch HIP events (the roofline entry) bracket every convolution launch of a SAMPLE of the timed steps - every 5th,
+    # Per-launch HIP events (the roofline entry, --full only) bracket every convolution launch of a SAMPLE of the timed steps - every 5th,
     # starting with the 3rd: an event record is a barrier packet on the launch stream, and 632 of them per step cost ~4 % of the
     # step (measured: 3190 vs 3330 frames/s), which would make the probe part of the result it measures.
+    full = getattr(args, "full", False)
+    if os.environ.get("LP_DUMP_LAUNCHES") and not full and rank == 0:
+        print("bench.py: LP_DUMP_LAUNCHES is set but the per-launch events are taken with --full only: no launch table is written",
+              file=sys.stderr, flush=True)
     prof_sink: list = []
     prof_steps = 0
     mem0 = torch.cuda.memory_stats(dev) if dev.type == "cuda" else {}
     t0 = time.perf_counter()
     for i in range(args.steps):
-        sampled = not args.no_profile and i % 5 == min(2, args.steps - 1)
+        sampled = full and not args.no_profile and dev.type == "cuda" and i % 5 == min(2, args.steps - 1)   # (HIP events: device only)
         model.net.profile = prof_sink if sampled else None
         prof_steps += int(sampled)
         loss = trainer.training_batch(model, batch, args.warmup + i)
@@ -547,12 +611,16 @@ def train_line(args, dev, rank: int, world: int) -> dict:
     elapsed = time.perf_counter() - t0
     prof = prof_sink
     model.net.profile = None
-    # host cost of one step when nothing throttles it: enqueue a step onto the idle GPU and stop the clock BEFORE synchronising
-    # (in the timed loop above the host runs ahead until the runtime's queue back-pressure paces it to the GPU)
-    t1 = time.perf_counter()
-    trainer.training_batch(model, batch, args.warmup + args.steps)
-    host_idle_queue = time.perf_counter() - t1
-    _sync(dev)
+    if getattr(args, "dump_outputs", None) and rank == 0 and not getattr(args, "_secondary", False):
+        dump_outputs(args.dump_outputs, step_outputs(model, loss))
+    host_idle_queue = None
+    if full:
+        # host cost of one step when nothing throttles it: enqueue a step onto the idle GPU and stop the clock BEFORE synchronising
+        # (in the timed loop above the host runs ahead until the runtime's queue back-pressure paces it to the GPU)
+        t1 = time.perf_counter()
+        trainer.training_batch(model, batch, args.warmup + args.steps)
+        host_idle_queue = time.perf_counter() - t1
+        _sync(dev)
     if dist.is_initialized():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -561,7 +629,8 @@ def train_line(args, dev, rank: int, world: int) -> dict:
 
     # what crosses GPUs per step: SyncBatchNorm all-reduces (one per BatchNorm layer and direction, both segments of the joint pass in one
     # message), the gradient buckets, one packed message of logged scalars
-    n_msgs = getattr(model.net, "sync_bn_messages", 0) // max(1, args.warmup + args.steps + 1)
+    steps_run = args.warmup + args.steps + (1 if host_idle_queue is not None else 0)   # every step this model took, the idle-queue one included
+    n_msgs = getattr(model.net, "sync_bn_messages", 0) // max(1, steps_run)
     # (the messages are lp_fxsum values - two int64 words = 16 B per sum - [segments = 2][2 sums][C] per BatchNorm layer, forward and backward)
     bn_bytes = sum(2 * 2 * b.C * 16 for b in getattr(model.net.plan, "bns", [])) * 2 if getattr(model.net, "sync_bn", False) else 0
     comm = {"sync_bn_messages": n_msgs, "sync_bn_bytes": bn_bytes, "grad_buckets": (0 if solo else -(-model.net.G.numel() * 4 // (64 << 20))),
@@ -586,7 +655,6 @@ def train_line(args, dev, rank: int, world: int) -> dict:
                    if args.views > 1 else f"training frames/sec (whole node), {arch} {args.size}x{args.size} {args.keypoints}-kp semi-sup"),
         "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1000 * elapsed / args.steps, 3), "host_enqueue_ms_per_step": round(1000 * host_enqueue / args.steps, 3),
-        "host_enqueue_idle_queue_ms": round(1000 * host_idle_queue, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32" if prec == "fp32" else "bf16", "data": "synthetic",
         "config": {"workload": (f"C5: multiview {arch} SemiSupervisedHeatmapTracker, {args.views} views x {args.size}x{args.size}, K={args.keypoints} per "
@@ -604,6 +672,8 @@ def train_line(args, dev, rank: int, world: int) -> dict:
                    "decode_prune": _decode_prune_label(model),
                    "final_loss": round(float(loss), 6)},
     }
+    if host_idle_queue is not None:
+        out["host_enqueue_idle_queue_ms"] = round(1000 * host_idle_queue, 3)
     if rank == 0:
         if prof:
             by: dict[str, list[float]] = {}
@@ -654,12 +724,12 @@ def train_line(args, dev, rank: int, world: int) -> dict:
         if gf and prec != "fp32":   # (the fp32 line runs on the fp32 MFMA pipe: not priced against the bf16 peak)
             out["model_tflops_per_gpu"] = round(value / world * gf / 1e3, 2)
             out["mfma_frac_end_to_end"] = round(value / world * gf / 1e3 / MFMA_BF16_PEAK_TFLOPS, 4)
-        if world == 1 and not dist.is_initialized() and not args.no_profile and args.views == 1 and not getattr(args, "_secondary", False):
+        if full and world == 1 and not dist.is_initialized() and not args.no_profile and args.views == 1 and not getattr(args, "_secondary", False):
             try:  # secondary rooflines; never allowed to cost the measured line
                 out["roofline_hbm"] = hbm_rooflines(dev, args.size, args.keypoints, args.labeled + args.unlabeled)
             except Exception as e:  # noqa: BLE001
                 out["roofline_hbm"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not dist.is_initialized() and not args.no_cpu_baseline and not is_vit and args.views == 1 and not getattr(args, "_secondary", False):
+        if full and world == 1 and not dist.is_initialized() and not args.no_cpu_baseline and not is_vit and args.views == 1 and not getattr(args, "_secondary", False):
             try:
                 out["cpu_baseline"] = cpu_baseline_in_subprocess(args.size, args.keypoints, args.cpu_baseline_steps)
             except Exception as e:  # noqa: BLE001 - the baseline must never cost the measured line
@@ -695,7 +765,7 @@ def main(argv: list[str] | None = None, device: torch.device | None = None) -> N
     """``device`` (tests only): run the whole flow on that device - the CPU with the emulated kernel library - instead of cuda:LOCAL_RANK."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=384)
     ap.add_argument("--labeled", type=int, default=64)
@@ -708,7 +778,7 @@ def main(argv: list[str] | None = None, device: torch.device | None = None) -> N
     ap.add_argument("--predict", action="store_true", help="secondary line: inference frames/s (eval mode, BatchNorm folded into the "
                     "convolutions, fused decode) over the same frames; the headline metric stays the training step")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false", help="skip the short secondary lines (256 px, ViT-S, multiview, "
-                    "inference) the default single-GPU run appends under \"secondary\"")
+                    "inference) a --full single-GPU run appends under \"secondary\"")
     ap.add_argument("--unfrozen", action="store_true", help="secondary line: the backbone group trains too (lr > 0), as after UnfreezeBackbone")
     ap.add_argument("--peaked", action="store_true", help="secondary line: head weights x200 -> peaked heat-maps as a trained head gives them "
                     "(the decode then picks its pruned kernels by itself, ops._DecodePruneAuto)")
@@ -719,9 +789,13 @@ def main(argv: list[str] | None = None, device: torch.device | None = None) -> N
     ap.add_argument("--fit", action="store_true", help="secondary line: Trainer.fit over the device-side producers (uint8 host frames -> "
                     "FrameWindowSource / LabeledBatchProducer / VideoFramePipeline -> step), i.e. what a user's training loop gets")
     ap.add_argument("--no-sync-bn", action="store_true", help="N > 1: per-rank BatchNorm statistics (the reference sets sync_batchnorm=True, train.py:427; A/B only)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-launch HIP events")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-launch HIP events")
     ap.add_argument("--syncbn-gather", action="store_true", help="N > 1: SyncBatchNorm messages as ONE all-gather + an ordered add of the ranks' rows "
                     "(int64 fixed-point sums) instead of an all-reduce (= LP_SYNCBN_GATHER=1; the A/B the first 8-GPU call decides)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the per-launch MFMA roofline (HIP "
+                    "events in the sampled steps), the heat-map HBM rooflines, the CPU baseline, the secondary lines, the idle-queue host step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed as "
+                    "DIR/<name>.npy (float32; parameters and gradients as a fixed, seeded sample)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) print the cpu_baseline object and exit: the reference's own "
                     "step when its modules are present (/root/reference, or oracle/_ref on the GPU box), the restated port otherwise")
     args = ap.parse_args(argv)
@@ -753,7 +827,7 @@ def main(argv: list[str] | None = None, device: torch.device | None = None) -> N
     out = train_line(args, dev, rank, world)
     if rank == 0:
         headline = (args.size, args.labeled, args.unlabeled, args.keypoints, args.views, args.backbone) == (384, 64, 128, 17, 1, "resnet50")
-        if args.secondary and world == 1 and not dist.is_initialized() and not args.predict and headline and dev.type == "cuda":
+        if args.full and args.secondary and world == 1 and not dist.is_initialized() and not args.predict and headline and dev.type == "cuda":
             # the other BASELINE.json configs / north_star sizes in the same run (short: 3 timed steps each), so the driver's BENCH file
             # holds them too; the headline stays `value`
             import copy
@@ -766,7 +840,7 @@ def main(argv: list[str] | None = None, device: torch.device | None = None) -> N
                               # the reference trains fp32 only (train.py:411-428): the same step at its precision, on the fp32 validation executor
                               ("resnet50_384_fp32", dict(precision="fp32", warmup=1, steps=2, no_profile=True))):
                 a2 = copy.copy(args)
-                a2.steps, a2.warmup, a2.no_cpu_baseline, a2._secondary = 3, 2, True, True
+                a2.steps, a2.warmup, a2.no_cpu_baseline, a2._secondary, a2.dump_outputs = 3, 2, True, True, None
                 for k_, v_ in over.items():
                     setattr(a2, k_, v_)
                 try:

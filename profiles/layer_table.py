@@ -1,8 +1,8 @@
 """Per-layer table of the convolution launches of one step: forward vs data gradient vs weight gradient, from the per-launch dump
 that bench.py writes when LP_DUMP_LAUNCHES=<file> is set (HIP events around every convolution C-ABI call of the last sampled step).
 
-    LP_DUMP_LAUNCHES=gpurun_out/launches.json python bench.py --steps 5 --no-cpu-baseline     # on the GPU box
-    python profiles/layer_table.py gpurun_out/launches.json                                    # anywhere
+    LP_DUMP_LAUNCHES=launches.json python bench.py --full --steps 5 --no-cpu-baseline     # on an MI355X
+    python profiles/layer_table.py launches.json                                          # anywhere
 
 Round 6: every launch record carries the NAME of the layer it belongs to (engine._timed(layer=...): the parameter name, e.g.
 backbone.5.0.conv1), and the table groups by it.  Until round 5 the table matched launches to layers by their ORDER in the step, and the

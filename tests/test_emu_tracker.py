@@ -173,9 +173,9 @@ def test_reference_default_backbone_name_and_mmpose_checkpoint(stack_backend, tm
 
 
 def test_reference_default_config_drives_the_registry(stack_backend, monkeypatch):
-    """scripts/configs/config_default.yaml of the reference (read here when /root/reference is present, else its relevant keys restated)
-    goes through get_loss_factories / get_model unchanged: backbone 'resnet50_animal_ap10k', heatmap_loss_type 'mse', the `losses`
-    hyper-parameter block, losses_to_use switching the semi-supervised class on."""
+    """scripts/configs/config_default.yaml of the reference (a copy in tests/golden/) goes through get_loss_factories / get_model
+    unchanged: backbone 'resnet50_animal_ap10k', heatmap_loss_type 'mse', the `losses` hyper-parameter block, losses_to_use switching the
+    semi-supervised class on."""
     import os
 
     import yaml
@@ -186,16 +186,8 @@ def test_reference_default_config_drives_the_registry(stack_backend, monkeypatch
 
     dev = stack_backend
     monkeypatch.setattr(heatmap_tracker, "_default_device", lambda: dev)
-    path = "/root/reference/scripts/configs/config_default.yaml"
-    if os.path.exists(path):
-        cfg = yaml.safe_load(open(path))
-    else:
-        cfg = {"data": {"mirrored_column_matches": None, "columns_for_singleview_pca": None},
-               "training": {"rng_seed_model_pt": 0, "optimizer": "Adam", "optimizer_params": {"learning_rate": 1e-3},
-                            "lr_scheduler": "multisteplr", "lr_scheduler_params": {"multisteplr": {"milestones": [150, 200, 250], "gamma": 0.5}}},
-               "model": {"losses_to_use": [], "backbone": "resnet50_animal_ap10k", "model_type": "heatmap", "heatmap_loss_type": "mse",
-                         "checkpoint": None},
-               "losses": {"temporal": {"log_weight": 11.0, "epsilon": 20.0, "prob_threshold": 0.05}}}
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config_default.yaml")) as fh:
+        cfg = yaml.safe_load(fh)
     assert cfg["model"]["backbone"] == "resnet50_animal_ap10k"
     cfg["data"].update(image_resize_dims={"height": 128, "width": 128}, num_keypoints=3, keypoint_names=["a", "b", "c"])
     cfg["model"]["backbone_pretrained"] = False  # (the default True needs the mmpose weights: see the checkpoint test above)

@@ -9,8 +9,8 @@ import torch
 
 from oracle import restated as O
 
-REF_DATA = "/root/reference/data/mirror-mouse-example"
-needs_reference_data = pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="bundled example data only exist in the build container")
+# the reference's bundled example project, as a fixture: its label file (90 frames, 17 keypoints) and the two images the tests load
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mirror-mouse-example")
 
 
 def _write_project(tmp_path, with_visible: bool, first_row_nan: bool = False):
@@ -75,7 +75,6 @@ def test_parse_label_csv_all_nan_first_row_is_data(tmp_path):
     np.testing.assert_array_equal(data.keypoints[1:].numpy(), xy[1:].astype(np.float32))
 
 
-@needs_reference_data
 def test_parse_label_csv_matches_the_verbatim_parser_on_the_bundled_labels(golden):
     """the labels the verbatim HeatmapDataset parsed (stored in tests/golden/labeled_targets.npz) come out of this parser too"""
     from lightning_pose_amd.data.datasets import parse_label_csv
@@ -121,7 +120,6 @@ def test_dataset_batches_on_the_device(stack_backend, tmp_path):
         HeatmapDataset(str(tmp_path), "CollectedData.csv", 128, 128, do_context=True, device=dev)
 
 
-@needs_reference_data
 def test_bundled_example_project_feeds_the_tracker(stack_backend):
     """the reference's own example project (grey-scale 406 x 396 PNGs, 17 keypoints with NaN labels) straight into a training step"""
     from lightning_pose_amd.data.datasets import HeatmapDataset
