@@ -50,7 +50,7 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * not only when symbols come or go.  lp_version() returns the value the library was built with; a caller compares the two before its first
  * call (lightning_pose_amd/_lib.py raises LpHipUnavailable on a mismatch) - a library built against an older header would otherwise take,
  * e.g., the stream argument for an inserted flag without any error.  History: 131 = round 5 (decode `prune`, bn_bwd `terms_ws`), 140 = round 6. */
-#define LP_HIP_ABI_VERSION 142
+#define LP_HIP_ABI_VERSION 143
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -573,6 +573,66 @@ int lp_frames_augment(const float* src_hwc, int S, int H, int W, const lp_frame_
 int lp_labeled_keypoints(const float* kp_src, const float* src_hw, const float* affine, const int* hflip, const int* swap,
                          const int* vis_in, int uniform_heatmaps, int B, int K, int H, int W, float* kp_out, int* vis_out,
                          lp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Labeled-frame augmentation (csrc/labelaug.hip): the imgaug "dlc" presets of data/augmentations.py:122-238, restated from imgaug's
+ * documented operator definitions (imgaug and OpenCV are not vendored: pixel parity with imgaug itself is UNPINNED).
+ * Every entry point is ONE launch sequence for the whole batch: `params` is a device array of B lp_labelaug_image (drawn on the host),
+ * an image whose flag for a stage is off is copied through.  u8 images are contiguous (B, H, W, 3); every stage rounds and saturates to
+ * uint8 as imgaug does between augmenters.  Continuous coordinates put the centre of pixel (i, j) at (j + 0.5, i + 0.5).
+ * Per-pixel randomness is Philox4x32-10 keyed by `seed` and counters (cell or pixel index, image_id | op << 16 | channel << 20 | what << 24):
+ * a value never depends on the launch geometry.
+ * ------------------------------------------------------------------------------------------------------ */
+enum { LP_AUG_GEOM = 1, LP_AUG_BLUR = 2, LP_AUG_DROPOUT = 4, LP_AUG_DROP_PER_CHANNEL = 8, LP_AUG_SALT = 16, LP_AUG_PEPPER = 32,
+       LP_AUG_ELASTIC = 64, LP_AUG_HISTEQ = 128, LP_AUG_CLAHE = 256, LP_AUG_EMBOSS = 512, LP_AUG_CROPPAD = 1024, LP_AUG_HFLIP = 2048 };
+enum { LP_AUG_OP_DROPOUT = 0, LP_AUG_OP_SALT = 1, LP_AUG_OP_PEPPER = 2, LP_AUG_OP_ELASTIC = 3 };   /* the `op` of the Philox counter */
+enum { LP_AUG_LOCAL_BLUR_COARSE = 0, LP_AUG_LOCAL_EMBOSS = 1 };
+#define LP_AUG_ELASTIC_MAX_RADIUS 20
+
+typedef struct lp_labelaug_image {   /* 60 four-byte words, no padding */
+    int flags;
+    int image_id;           /* the image's number in the Philox counters (its index in the batch it was drawn for; < 65536)              */
+    float geom[6];          /* LP_AUG_GEOM: row-major (2,3) DESTINATION -> SOURCE map of Rot90 then Affine on continuous coordinates      */
+    float blur[25];         /* LP_AUG_BLUR: 5 x 5 correlation weights (MotionBlur's rotated line, sum 1), border reflect-101             */
+    float emboss[9];        /* LP_AUG_EMBOSS: 3 x 3 correlation weights, (1 - alpha) identity + alpha emboss(strength)                    */
+    int coarse_gh[3], coarse_gw[3];  /* grid of CoarseDropout / CoarseSalt / CoarsePepper; pixel (y, x) lies in cell (y gh / H, x gw / W)  */
+    unsigned coarse_thr[3]; /* a cell is masked when (Philox word >> 8) < thr, thr = p 2^24                                              */
+    float elastic_alpha;    /* LP_AUG_ELASTIC: displacement = alpha * Gaussian-filtered U(-1, 1) noise                                    */
+    int clahe_clip, clahe_tiles_y, clahe_tiles_x, clahe_slot; /* clip count per bin (>= 1), tile grid, index into the look-up-table buffer */
+    int pad[4];             /* LP_AUG_CROPPAD: top, right, bottom, left in px; positive pads with zeros, negative crops                  */
+} lp_labelaug_image;
+
+/* Rot90 and Affine as one inverse-mapped bilinear gather with zero fill */
+int lp_labelaug_geom(const void* src_u8, int B, int H, int W, const lp_labelaug_image* params, void* dst_u8, lp_stream_t stream);
+/* which = LP_AUG_LOCAL_BLUR_COARSE: MotionBlur -> CoarseDropout -> CoarseSalt -> CoarsePepper;  LP_AUG_LOCAL_EMBOSS: Emboss.  One stencil
+ * pass over an LDS tile with a 2-pixel halo; the coarse masks are evaluated per pixel from the cell index.  salt_lut: 256 bytes, the
+ * quantile table of the salt value (pepper = 255 - salt), indexed by the top byte of the pixel's Philox word. */
+int lp_labelaug_local(const void* src_u8, int B, int H, int W, const lp_labelaug_image* params, int which, const void* salt_lut,
+                      unsigned long long seed, void* dst_u8, lp_stream_t stream);
+/* field fp32 (B, 2, H, W) = (dx, dy) = alpha * G_sigma * U(-1, 1) for the images with LP_AUG_ELASTIC (others: not written); the Gaussian is
+ * cut at 4 sigma (<= LP_AUG_ELASTIC_MAX_RADIUS taps each side), border reflect-101; tmp: workspace of the same size */
+int lp_labelaug_elastic_field(int B, int H, int W, const lp_labelaug_image* params, float sigma, unsigned long long seed, float* tmp,
+                              float* field, lp_stream_t stream);
+/* dst(x, y) = bicubic (Keys, A = -0.75) sample of src at (x + dx, y + dy), taps outside the image read 0 */
+int lp_labelaug_elastic_apply(const void* src_u8, int B, int H, int W, const lp_labelaug_image* params, const float* field, void* dst_u8,
+                              lp_stream_t stream);
+/* 256-bin equalisation per channel: lut[v] = round(255 (cdf[v] - cdf_min) / (n - cdf_min)) in integers.  ws: B*3*256 unsigned (zeroed
+ * here); lut_out: B*3*256 bytes (written for the images with LP_AUG_HISTEQ) */
+int lp_labelaug_histeq(const void* src_u8, int B, int H, int W, const lp_labelaug_image* params, unsigned* ws, void* lut_out, void* dst_u8,
+                       lp_stream_t stream);
+/* CLAHE per channel: tiles of ceil(H / tiles_y) x ceil(W / tiles_x) px over the image extended by reflection-101, histogram clipped at
+ * clahe_clip with the excess redistributed, lut = round(255 cdf / area) in integers, bilinear blend of the four nearest tiles' tables.
+ * slot_image (n_slots): image index of each look-up-table slot; luts: n_slots * max_ty * max_tx * 3 * 256 bytes */
+int lp_labelaug_clahe(const void* src_u8, int B, int H, int W, const lp_labelaug_image* params, const int* slot_image, int n_slots,
+                      int max_ty, int max_tx, void* luts, void* dst_u8, lp_stream_t stream);
+/* CropAndPad (keep_size=False) -> cubic Resize to (H, W) (lp_frames_resize_cubic's arithmetic on the cropped / zero-padded image) ->
+ * /255 -> normalise -> optional mirrored write (LP_AUG_HFLIP): fp32 (B, 3, H, W) */
+int lp_labelaug_finish(const void* src_u8, int B, int Hs, int Ws, const lp_labelaug_image* params, int H, int W, const lp_frame_norm* norm,
+                       float* dst, lp_stream_t stream);
+/* kp (B,K,2) source px -> affine (B,2,3) (NULL: identity) -> minus the displacement sampled (bilinear) at the moved point for images with
+ * LP_AUG_ELASTIC when field != NULL (first-order inverse of the elastic map).  NaN stays NaN.  kp_out must not alias kp. */
+int lp_labelaug_keypoints(const float* kp, int B, int K, const float* affine, const lp_labelaug_image* params, const float* field, int H,
+                          int W, float* kp_out, lp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Optimiser: torch.optim.Adam / AdamW semantics (models/base.py:458-479) over one flat fp32 range, also emitting

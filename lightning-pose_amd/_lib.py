@@ -54,9 +54,15 @@ HM_MSE, HM_KL, HM_JS = 0, 1, 2
 CONV_KERNEL_IGEMM, CONV_KERNEL_PIPE, CONV_KERNEL_WGRAD, CONV_KERNEL_WGRAD_PIPE, CONV_KERNEL_PIPE_HALO, CONV_KERNEL_RES2D = 0, 1, 2, 3, 4, 5   # lp_conv_last_kernel()
 CONV_KERNEL_STEM_WGRAD_NB = 8
 BORDER_RENORM, BORDER_CLAMP = 0, 1
+# include/lp_hip.h: LP_AUG_* flags, Philox op numbers, lp_labelaug_local's `which`
+AUG_GEOM, AUG_BLUR, AUG_DROPOUT, AUG_DROP_PER_CHANNEL, AUG_SALT, AUG_PEPPER = 1, 2, 4, 8, 16, 32
+AUG_ELASTIC, AUG_HISTEQ, AUG_CLAHE, AUG_EMBOSS, AUG_CROPPAD, AUG_HFLIP = 64, 128, 256, 512, 1024, 2048
+AUG_OP_DROPOUT, AUG_OP_SALT, AUG_OP_PEPPER, AUG_OP_ELASTIC = 0, 1, 2, 3
+AUG_LOCAL_BLUR_COARSE, AUG_LOCAL_EMBOSS = 0, 1
+AUG_ELASTIC_MAX_RADIUS = 20
 TF_NONE, TF_SINGLE, TF_PER_FRAME, TF_PER_VIEW = 0, 1, 2, 3
 
-ABI_VERSION = 142   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
+ABI_VERSION = 143   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -151,6 +157,14 @@ PROTOTYPES = {
     "lp_frames_resize_cubic": (_I, [_P, _I, _I, _I, C.c_longlong, _I, _I, _I, _I, C.POINTER(FrameNorm), _P, _P]),
     "lp_frames_augment": (_I, [_P, _I, _I, _I, C.POINTER(FrameAugment), C.POINTER(FrameNorm), _P, _P]),
     "lp_labeled_keypoints": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "lp_labelaug_geom": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "lp_labelaug_local": (_I, [_P, _I, _I, _I, _P, _I, _P, C.c_ulonglong, _P, _P]),
+    "lp_labelaug_elastic_field": (_I, [_I, _I, _I, _P, _F, C.c_ulonglong, _P, _P, _P]),
+    "lp_labelaug_elastic_apply": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    "lp_labelaug_histeq": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "lp_labelaug_clahe": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "lp_labelaug_finish": (_I, [_P, _I, _I, _I, _P, _I, _I, C.POINTER(FrameNorm), _P, _P]),
+    "lp_labelaug_keypoints": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
     "lp_f32_conv_fwd": (_I, [_P, _P, C.POINTER(ConvGeom), _I, _I, _I, _P, _P, _P, _P]),
     "lp_f32_conv_dgrad": (_I, [_P, _P, C.POINTER(ConvGeom), _I, _I, _I, _P, _P, _P, _P]),
     "lp_f32_conv_wgrad": (_I, [_P, _P, C.POINTER(ConvGeom), _I, _I, _I, _P, _P]),

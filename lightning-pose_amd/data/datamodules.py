@@ -6,7 +6,8 @@ Same constructor arguments and attributes (``dataset``, ``train_dataset`` / ``va
 ``torch.utils.data.random_split`` under ``torch.Generator().manual_seed(torch_seed)``, so the same seed selects the same examples as the
 reference.  The loaders yield ``HeatmapLabeledBatchDict``s built on the device by the dataset (no worker processes: nothing but the decoded
 uint8 images is prepared on the host); the training loader shuffles with the reference's generator (``torch.randperm`` under
-``manual_seed(torch_seed)``, continued across epochs), validation / test / full loaders run in order and never flip.
+``manual_seed(torch_seed)``, continued across epochs), validation / test / full loaders run in order and never flip or augment
+(the dataset's ``imgaug_transform`` is applied by the training loader only).
 """
 
 from __future__ import annotations
@@ -47,8 +48,9 @@ class BaseDataModule:
 
     def _ordered(self, indices, batch_size: int) -> Iterator[dict]:
         for lo in range(0, len(indices), batch_size):
+            kw = {"augment": False} if getattr(self.dataset, "imgaug_transform", None) is not None else {}  # never augmented (reference :130-183)
             yield self.dataset.batch(list(indices[lo:lo + batch_size]), hflip=torch.zeros(len(indices[lo:lo + batch_size]), dtype=torch.bool)
-                                     if getattr(self.dataset, "imgaug_hflip", False) else None)
+                                     if getattr(self.dataset, "imgaug_hflip", False) else None, **kw)
 
     def _rank_world(self) -> tuple[int, int]:
         import torch.distributed as dist

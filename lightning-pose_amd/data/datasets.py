@@ -9,8 +9,10 @@ consumes - same constructor arguments, attributes (``keypoints``, ``visibility``
 What differs is where the work happens: the reference transforms one sample at a time in DataLoader workers (PIL -> imgaug -> ToTensor ->
 Normalize -> ``generate_heatmaps`` on the CPU) and ships fp32 images plus fp32 targets to the GPU; here only the decoded uint8 images cross
 PCIe and ``LabeledBatchProducer`` builds the whole ``HeatmapLabeledBatchDict`` on the device (resize + normalise, keypoint projection,
-optional flip with the left / right swap, out-of-frame -> NaN, Gaussian targets).  The imgaug augmentation zoo and context (5-frame)
-loading are outside this path.
+optional flip with the left / right swap, out-of-frame -> NaN, Gaussian targets).  ``imgaug_transform`` is the device pipeline that
+``data.augmentations.imgaug_transform`` / ``get_imgaug_transform`` build from ``cfg.training.imgaug`` (the reference's ``iaa.Sequential``
+in the same argument): it is drawn once per batch on the host and applied to the uint8 images on the device before the resize; the
+validation / test / prediction loaders ask for ``augment=False``.  Context (5-frame) loading is outside this path.
 """
 
 from __future__ import annotations
@@ -84,7 +86,8 @@ class HeatmapDataset:
 
     def __init__(self, root_directory: str, csv_path: str, image_resize_height: int, image_resize_width: int,
                  header_rows: list[int] | None = [0, 1, 2], downsample_factor: int = 2, do_context: bool = False,
-                 uniform_heatmaps: bool = False, imgaug_hflip: bool = False, device: torch.device | str | None = None) -> None:
+                 uniform_heatmaps: bool = False, imgaug_hflip: bool = False, device: torch.device | str | None = None,
+                 imgaug_transform=None) -> None:
         if do_context:
             raise NotImplementedError("context (5-frame) datasets belong to the MHCRNN models, outside the MI355X heatmap-tracker path")
         self.root_directory = str(root_directory)
@@ -110,6 +113,9 @@ class HeatmapDataset:
         self.device = torch.device(device) if device is not None else torch.device(f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}")
         self._stage = HostStager(self.device)
         self._rng = np.random.default_rng(0)
+        if imgaug_transform is not None and not (hasattr(imgaug_transform, "draw") and hasattr(imgaug_transform, "run")):
+            raise TypeError(f"imgaug_transform must be a data.augmentations.LabeledAugmentation, got {type(imgaug_transform)}")
+        self.imgaug_transform = imgaug_transform
 
     @property
     def height(self) -> int:
@@ -138,14 +144,18 @@ class HeatmapDataset:
             raise ValueError(f"images of one batch must share a size, got {sorted({f.shape for f in frames})}")
         return torch.from_numpy(np.stack(frames))
 
-    def batch(self, indices: Sequence[int], hflip: torch.Tensor | None = None) -> HeatmapLabeledBatchDict:
-        """The labeled batch of the step for these examples; ``hflip`` (B,) overrides the random flip decisions of ``imgaug_hflip``."""
+    def batch(self, indices: Sequence[int], hflip: torch.Tensor | None = None, augment: bool = True) -> HeatmapLabeledBatchDict:
+        """The labeled batch of the step for these examples; ``hflip`` (B,) overrides the random flip decisions of ``imgaug_hflip``;
+        ``augment=False`` leaves ``imgaug_transform`` out (validation, test, prediction)."""
         idx = torch.as_tensor(list(indices), dtype=torch.long)
         images = self._stage(self.load_images(idx.tolist()))   # pinned staging + copy stream: overlaps the step that is running
         if hflip is None and self.imgaug_hflip:
             hflip = torch.from_numpy(self._rng.random(len(idx)) < 0.5)  # each sample flips with probability 0.5 (reference :275)
+        drawn = None
+        if augment and self.imgaug_transform is not None and len(self.imgaug_transform) > 0:  # (0 operators: resize only)
+            drawn = self.imgaug_transform.draw(len(idx), int(images.shape[1]), int(images.shape[2]))
         return self.producer(images, self.keypoints[idx].to(self.device), idxs=idx, visibility=self.visibility[idx].to(self.device),
-                             hflip=hflip)
+                             hflip=hflip, augment=drawn)
 
     def batches(self, batch_size: int, shuffle: bool = True, seed: int = 0, drop_last: bool = False) -> Iterator[HeatmapLabeledBatchDict]:
         order = np.random.default_rng(seed).permutation(len(self)) if shuffle else np.arange(len(self))

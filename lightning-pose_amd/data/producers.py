@@ -29,7 +29,7 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from .. import ops
+from .. import _lib, ops
 from .datatypes import HeatmapLabeledBatchDict, MultiviewUnlabeledBatchDict, UnlabeledBatchDict
 
 _IMAGENET_MEAN = [0.485, 0.456, 0.406]  # reference data/__init__.py:46-47
@@ -138,15 +138,21 @@ class LabeledBatchProducer:
 
     def __call__(self, images_u8: torch.Tensor, keypoints: torch.Tensor, idxs: torch.Tensor | None = None,
                  visibility: torch.Tensor | None = None, bbox: torch.Tensor | None = None, affine: torch.Tensor | None = None,
-                 hflip: torch.Tensor | None = None) -> HeatmapLabeledBatchDict:
+                 hflip: torch.Tensor | None = None, augment: dict | None = None) -> HeatmapLabeledBatchDict:
         """images_u8 (B, Hs, Ws, 3) uint8 on the device; keypoints (B, 2K) or (B, K, 2) in source px (NaN = unlabeled);
-        optional per-sample augmentation ``affine`` (B, 2, 3) on source px (applied to image and labels alike) and ``hflip`` (B)."""
+        optional per-sample augmentation ``affine`` (B, 2, 3) on source px (applied to image and labels alike) and ``hflip`` (B).
+        ``augment``: one batch's draw of a ``LabeledAugmentation`` (``pipeline.draw(B, Hs, Ws)``, or a kept one to replay it): the imgaug
+        operators run on the uint8 images, then crop-and-pad + cubic resize + normalise + flip in one launch, and the keypoints follow the
+        same geometry (``hflip`` is then read on the HOST, it goes into the parameter table: pass a CPU tensor, a device tensor costs a
+        synchronising copy).  With ``None`` nothing below changes."""
         dev = images_u8.device
         b, hs, ws, _ = images_u8.shape
         kp = keypoints.reshape(b, -1, 2).to(dev)
         k = kp.shape[1]
         if self.swap is not None and sorted(self.swap.tolist()) != list(range(k)):  # host-side list: checked before it indexes on the device
             raise ValueError(f"hflip_swap_indices must be a permutation of range({k}), got {self.swap.tolist()}")
+        if augment is not None:
+            return self._augmented(images_u8, kp, idxs, visibility, bbox, affine, hflip, augment)
         src_hw = torch.tensor([[float(hs), float(ws)]], device=dev).repeat(b, 1)
         kp_model, vis = ops.labeled_keypoints(kp, src_hw, self.height, self.width, affine=affine, hflip=hflip, swap=self.swap,
                                               visibility=visibility, uniform_heatmaps=self.uniform_heatmaps)
@@ -172,6 +178,39 @@ class LabeledBatchProducer:
                 planes.append(ops.frames_augment(raw[i:i + 1], self.mean, self.std, matrix=m[:2]))
             images = torch.cat(planes, 0)
         if bbox is None:  # x, y, h, w of the whole source frame (reference :352-356)
+            bbox = torch.tensor([[0.0, 0.0, float(hs), float(ws)]], device=dev).repeat(b, 1)
+        if idxs is None:
+            idxs = torch.arange(b)
+        return HeatmapLabeledBatchDict(images=images, keypoints=kp_model.reshape(b, 2 * k), heatmaps=heatmaps, bbox=bbox.to(dev), idxs=idxs)
+
+
+    def _augmented(self, images_u8, kp, idxs, visibility, bbox, affine, hflip, augment: dict) -> HeatmapLabeledBatchDict:
+        """the batch through a drawn ``LabeledAugmentation``: a fixed number of launches, whatever the batch size"""
+        if affine is not None:
+            raise ValueError("affine and augment are two ways to say the same thing: give one")
+        if self.interpolation != "cubic":
+            raise NotImplementedError("augment needs interpolation='cubic' (imgaug's Resize)")
+        dev = images_u8.device
+        b, hs, ws, _ = images_u8.shape
+        k = kp.shape[1]
+        table = augment["table"].copy()
+        if len(table) != b:
+            raise ValueError(f"the drawn table has {len(table)} rows for a batch of {b}")
+        if hflip is not None:  # the flip comes after the imgaug pipeline, in model pixels (reference data/datasets.py:288-293)
+            table["flags"] |= np.where(hflip.cpu().numpy().astype(bool), _lib.AUG_HFLIP, 0).astype(np.int32)
+        table_dev = ops.labelaug_table(table, dev)
+        raw, field = augment["pipeline"].run(images_u8, augment, table_dev)
+        images = ops.labelaug_finish(raw, table_dev, self.height, self.width, self.mean, self.std)
+        # keypoints: Rot90 / Affine (one matrix), the elastic displacement, then crop-and-pad's offset and the resize of the new frame
+        moved = ops.labelaug_keypoints(kp, torch.from_numpy(augment["affine"][:, :2].astype(np.float32)).to(dev), table_dev, field, hs, ws)
+        pad = np.where((table["flags"] & _lib.AUG_CROPPAD)[:, None] != 0, table["pad"], 0).astype(np.float32)  # top, right, bottom, left
+        src_hw = torch.from_numpy(np.stack([hs + pad[:, 0] + pad[:, 2], ws + pad[:, 1] + pad[:, 3]], 1)).to(dev)
+        shift = np.tile(np.eye(3, dtype=np.float32)[:2], (b, 1, 1))
+        shift[:, 0, 2], shift[:, 1, 2] = pad[:, 3], pad[:, 0]
+        kp_model, vis = ops.labeled_keypoints(moved, src_hw, self.height, self.width, affine=torch.from_numpy(shift).to(dev), hflip=hflip,
+                                              swap=self.swap, visibility=visibility, uniform_heatmaps=self.uniform_heatmaps)
+        heatmaps = ops.generate_heatmaps(kp_model, self.height, self.width, self.output_shape, self.output_sigma, vis)
+        if bbox is None:
             bbox = torch.tensor([[0.0, 0.0, float(hs), float(ws)]], device=dev).repeat(b, 1)
         if idxs is None:
             idxs = torch.arange(b)

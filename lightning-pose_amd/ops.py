@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import functools
+from typing import Sequence
 
 import numpy as np
 import torch
@@ -676,3 +677,129 @@ def labeled_keypoints(keypoints: torch.Tensor, src_hw: torch.Tensor, height: int
     check(_lib.lib().lp_labeled_keypoints(_p(kp), _p(hw), _p(aff), _p(fl), _p(sw), _p(vi), int(uniform_heatmaps), b, k, int(height),
                                           int(width), _p(out), _p(vis), _stream()), "lp_labeled_keypoints")
     return out, vis
+
+
+# --------------------------------------------------------------------------------------------------------
+# labeled-frame augmentation (csrc/labelaug.hip): one parameter table per batch, one launch sequence per stage
+# --------------------------------------------------------------------------------------------------------
+
+# include/lp_hip.h: lp_labelaug_image, field for field (60 four-byte words)
+LABELAUG_DTYPE = np.dtype([("flags", "<i4"), ("image_id", "<i4"), ("geom", "<f4", (6,)), ("blur", "<f4", (25,)), ("emboss", "<f4", (9,)),
+                           ("coarse_gh", "<i4", (3,)), ("coarse_gw", "<i4", (3,)), ("coarse_thr", "<u4", (3,)), ("elastic_alpha", "<f4"),
+                           ("clahe_clip", "<i4"), ("clahe_tiles_y", "<i4"), ("clahe_tiles_x", "<i4"), ("clahe_slot", "<i4"),
+                           ("pad", "<i4", (4,))])
+assert LABELAUG_DTYPE.itemsize == 60 * 4
+
+
+def salt_quantiles() -> np.ndarray:
+    """The 256-entry quantile table of the value imgaug's CoarseSalt writes, 255 (0.5 + |Beta(0.5, 0.5) - 0.5|) = 127.5 + 127.5 |cos(pi u)|
+    at u = (i + 0.5) / 256 (CoarsePepper: 255 minus it)."""
+    u = (np.arange(256) + 0.5) / 256.0
+    return np.floor(127.5 + 127.5 * np.abs(np.cos(np.pi * u)) + 0.5).clip(0, 255).astype(np.uint8)
+
+
+def labelaug_table(table: np.ndarray, device) -> torch.Tensor:
+    """host parameter table (LABELAUG_DTYPE, one row per image) -> the device bytes the labelaug_* wrappers take"""
+    if table.dtype != LABELAUG_DTYPE or table.ndim != 1:
+        raise ValueError(f"table must be a 1-D array of ops.LABELAUG_DTYPE, got {table.dtype} {table.shape}")
+    return torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).copy()).to(device)
+
+
+def _aug_images(images_u8: torch.Tensor, table: torch.Tensor) -> tuple[torch.Tensor, int, int, int]:
+    require_device(images_u8, table)
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise ValueError(f"images must be uint8 (B, H, W, 3), got {images_u8.dtype} {tuple(images_u8.shape)}")
+    b, h, w, _ = images_u8.shape
+    if table.dtype != torch.uint8 or table.numel() != b * LABELAUG_DTYPE.itemsize:
+        raise ValueError(f"table must hold {b} rows of {LABELAUG_DTYPE.itemsize} bytes (ops.labelaug_table)")
+    return images_u8.contiguous(), b, h, w
+
+
+def labelaug_geom(images_u8: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """Rot90 + Affine: one bilinear gather through the table's destination -> source maps (fill 0)"""
+    x, b, h, w = _aug_images(images_u8, table)
+    out = torch.empty_like(x)
+    check(_lib.lib().lp_labelaug_geom(_p(x), b, h, w, _p(table), _p(out), _stream()), "lp_labelaug_geom")
+    return out
+
+
+def labelaug_local(images_u8: torch.Tensor, table: torch.Tensor, which: int, seed: int = 0, salt_lut: torch.Tensor | None = None) -> torch.Tensor:
+    """which = _lib.AUG_LOCAL_BLUR_COARSE: MotionBlur -> CoarseDropout -> CoarseSalt -> CoarsePepper; _lib.AUG_LOCAL_EMBOSS: Emboss"""
+    x, b, h, w = _aug_images(images_u8, table)
+    if which == _lib.AUG_LOCAL_BLUR_COARSE and salt_lut is None:
+        salt_lut = torch.from_numpy(salt_quantiles()).to(x.device)
+    out = torch.empty_like(x)
+    check(_lib.lib().lp_labelaug_local(_p(x), b, h, w, _p(table), int(which), _p(salt_lut), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(out),
+                                       _stream()), "lp_labelaug_local")
+    return out
+
+
+def labelaug_elastic_field(table: torch.Tensor, b: int, h: int, w: int, sigma: float, seed: int = 0) -> torch.Tensor:
+    """fp32 (B, 2, H, W) displacement (dx, dy) of the images whose ELASTIC flag is set (zero elsewhere)"""
+    require_device(table)
+    tmp = torch.empty(b, 2, h, w, device=table.device, dtype=torch.float32)
+    field = torch.zeros(b, 2, h, w, device=table.device, dtype=torch.float32)
+    check(_lib.lib().lp_labelaug_elastic_field(int(b), int(h), int(w), _p(table), float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(tmp),
+                                               _p(field), _stream()), "lp_labelaug_elastic_field")
+    return field
+
+
+def labelaug_elastic_apply(images_u8: torch.Tensor, table: torch.Tensor, field: torch.Tensor) -> torch.Tensor:
+    """out(x, y) = bicubic sample of the image at (x + dx, y + dy), zero outside"""
+    x, b, h, w = _aug_images(images_u8, table)
+    f = _f32c(field)
+    if f.shape != (b, 2, h, w):
+        raise ValueError(f"field must be (B, 2, H, W) = {(b, 2, h, w)}, got {tuple(f.shape)}")
+    out = torch.empty_like(x)
+    check(_lib.lib().lp_labelaug_elastic_apply(_p(x), b, h, w, _p(table), _p(f), _p(out), _stream()), "lp_labelaug_elastic_apply")
+    return out
+
+
+def labelaug_histeq(images_u8: torch.Tensor, table: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """AllChannelsHistogramEqualization -> (images, the (B, 3, 256) uint8 look-up tables; rows of images without the flag are zero)"""
+    x, b, h, w = _aug_images(images_u8, table)
+    ws = torch.empty(b * 768, device=x.device, dtype=torch.int32)
+    lut = torch.zeros(b, 3, 256, device=x.device, dtype=torch.uint8)
+    out = torch.empty_like(x)
+    check(_lib.lib().lp_labelaug_histeq(_p(x), b, h, w, _p(table), _p(ws), _p(lut), _p(out), _stream()), "lp_labelaug_histeq")
+    return out, lut
+
+
+def labelaug_clahe(images_u8: torch.Tensor, table: torch.Tensor, slot_image: Sequence[int], max_ty: int, max_tx: int) -> torch.Tensor:
+    """AllChannelsCLAHE; ``slot_image[s]`` = the image whose table row says ``clahe_slot == s`` (host knowledge: no read-back)"""
+    x, b, h, w = _aug_images(images_u8, table)
+    n = len(slot_image)
+    slots = torch.tensor(list(slot_image), dtype=torch.int32).to(x.device) if n else None
+    luts = torch.empty(max(n, 1) * max(max_ty, 1) * max(max_tx, 1) * 768, device=x.device, dtype=torch.uint8)
+    out = torch.empty_like(x)
+    check(_lib.lib().lp_labelaug_clahe(_p(x), b, h, w, _p(table), _p(slots), n, int(max_ty), int(max_tx), _p(luts), _p(out), _stream()),
+          "lp_labelaug_clahe")
+    return out
+
+
+def labelaug_finish(images_u8: torch.Tensor, table: torch.Tensor, height: int, width: int, mean, std) -> torch.Tensor:
+    """CropAndPad -> cubic Resize -> /255 -> normalise -> optional mirror: fp32 (B, 3, height, width)"""
+    x, b, hs, ws = _aug_images(images_u8, table)
+    norm = _frame_norm(mean, std)
+    out = torch.empty(b, 3, int(height), int(width), device=x.device, dtype=torch.float32)
+    check(_lib.lib().lp_labelaug_finish(_p(x), b, hs, ws, _p(table), int(height), int(width), C.byref(norm), _p(out), _stream()),
+          "lp_labelaug_finish")
+    return out
+
+
+def labelaug_keypoints(keypoints: torch.Tensor, affine: torch.Tensor | None, table: torch.Tensor | None, field: torch.Tensor | None,
+                       h: int, w: int) -> torch.Tensor:
+    """(B, K, 2) source-px labels through the (B, 2, 3) affine of Rot90 / Affine and, with ``field``, the elastic displacement"""
+    require_device(keypoints)
+    kp = _f32c(keypoints)
+    b, k, _ = kp.shape
+    aff = None if affine is None else _f32c(affine.to(kp.device))
+    if aff is not None and aff.shape != (b, 2, 3):
+        raise ValueError("labelaug_keypoints: affine must be (B, 2, 3)")
+    f = None if field is None else _f32c(field)
+    if f is not None and (f.shape != (b, 2, h, w) or table is None):
+        raise ValueError("labelaug_keypoints: field must be (B, 2, H, W) and comes with its table")
+    out = torch.empty_like(kp)
+    check(_lib.lib().lp_labelaug_keypoints(_p(kp), b, k, _p(aff), _p(table), _p(f), int(h), int(w), _p(out), _stream()),
+          "lp_labelaug_keypoints")
+    return out
