@@ -49,8 +49,9 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
 /* ABI version of THIS header: bumped whenever the signature of an existing entry point changes (an argument inserted, a struct field added),
  * not only when symbols come or go.  lp_version() returns the value the library was built with; a caller compares the two before its first
  * call (lightning_pose_amd/_lib.py raises LpHipUnavailable on a mismatch) - a library built against an older header would otherwise take,
- * e.g., the stream argument for an inserted flag without any error.  History: 131 = round 5 (decode `prune`, bn_bwd `terms_ws`), 140 = round 6. */
-#define LP_HIP_ABI_VERSION 143
+ * e.g., the stream argument for an inserted flag without any error.  History: 131 = round 5 (decode `prune`, bn_bwd `terms_ws`), 140 = round 6,
+ * 144 = the multi-view token assembly (lp_vit_mv_tokens_*). */
+#define LP_HIP_ABI_VERSION 144
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -388,6 +389,10 @@ int lp_f32_softmax2d_bwd(const float* prob, const float* gprob, int B, int K, in
 int lp_f32_vit_patchify(const float* images, int B, int H, int W, int patch, float* out, lp_stream_t stream);
 int lp_f32_vit_tokens_fwd(const float* patch, const float* cls, const float* pos, int B, int Np, int D, float* x, lp_stream_t stream);
 int lp_f32_vit_tokens_bwd(const float* dx, int B, int Np, int D, float* dpatch, float* dpos, lp_stream_t stream);
+/* fp32 forms of lp_vit_mv_tokens_fwd / _bwd (below): patch and dpatch in float, the same workspace (lp_vit_mv_tokens_bwd_workspace_bytes) */
+int lp_f32_vit_mv_tokens_fwd(const float* patch, const float* pos, const float* view, int B, int V, int Np, int D, float* x, lp_stream_t stream);
+int lp_f32_vit_mv_tokens_bwd(const float* dx, int B, int V, int Np, int D, float* dpatch, float* dpos, float* dview, void* workspace,
+                             size_t workspace_bytes, lp_stream_t stream);
 int lp_f32_layernorm_fwd(const float* x, const float* delta, float* x_out, const float* gamma, const float* beta, float eps, int M, int D,
                          int drop_T, float* y, float* mean, float* rstd, lp_stream_t stream);
 int lp_f32_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, int M, int D, int drop_T,
@@ -501,6 +506,22 @@ int lp_vit_patchify(const float* images_nchw, int B, int H, int W, int patch, vo
 int lp_vit_tokens_fwd(const void* patch_bf16, const float* cls, const float* pos, int B, int Np, int D, float* x, lp_stream_t stream);
 /* dpatch = bf16(dx[:, 1:]);  dpos[t] = sum_b dx[b][t]  (d cls = dpos[0]) */
 int lp_vit_tokens_bwd(const float* dx, int B, int Np, int D, void* dpatch_bf16, float* dpos, lp_stream_t stream);
+/* Token assembly of the multi-view transformer tracker (models/heatmap_tracker_multiview.py:143-223 forward_vit: ViTEmbeddings(...)[:, 1:]
+ * + view_embeddings[v], reshaped to (B, V*Np, D)): no [CLS] row; row (b*V + v)*Np + p of `patch` becomes token v*Np + p of sample b.
+ *   x[b][v*Np + p][:] = (patch[(b*V + v)*Np + p][:] + pos[1 + p][:]) + view[v][:]      - fp32, the two additions in THIS order
+ * pos: the interpolated (1 + Np, D) table (row 0, the [CLS] position, is not read); view (V, D).  D must be a multiple of 64
+ * (LP_ERR_UNSUPPORTED otherwise). */
+int lp_vit_mv_tokens_fwd(const void* patch_bf16, const float* pos, const float* view, int B, int V, int Np, int D, float* x,
+                         lp_stream_t stream);
+/* Backward, one pass over dx (B*V*Np, D): dpatch = bf16(dx) (round to nearest even; same row order),
+ * dpos (1 + Np, D): dpos[0] = 0, dpos[1 + p] = sum_{b,v} dx;  dview (V, D): dview[v] = sum_{b,p} dx.  All three are WRITTEN, not
+ * accumulated.  The sums are a two-level reduction in a fixed order (workgroup partials in `workspace`, combined by a second small
+ * launch; no floating-point atomics): the same input gives the same bits.  workspace: lp_vit_mv_tokens_bwd_workspace_bytes(B, V, Np, D)
+ * bytes (0 for an unsupported shape), contents undefined before and after.  D must be a multiple of 64 and V * ceil(B / group) <= 65535
+ * (LP_ERR_UNSUPPORTED); a null pointer, a non-positive dimension or a workspace that is too small: LP_ERR_ARGUMENT. */
+size_t lp_vit_mv_tokens_bwd_workspace_bytes(int B, int V, int Np, int D);
+int lp_vit_mv_tokens_bwd(const float* dx, int B, int V, int Np, int D, void* dpatch_bf16, float* dpos, float* dview, void* workspace,
+                         size_t workspace_bytes, lp_stream_t stream);
 /* y (R,D) (+)= w (R,Q) @ x (Q,D), or with transpose_w: y (Q,D) (+)= w^T @ x (R,D): bicubic position-embedding interpolation */
 int lp_small_matmul(const float* w, const float* x, int R, int Q, int D, int transpose_w, int accumulate, float* y, lp_stream_t stream);
 /* x_out = x (+ delta_bf16);  y = LayerNorm(x_out) in bf16;  drop_T > 0: rows with row % drop_T == 0 ([CLS]) are dropped from y and

@@ -62,7 +62,7 @@ AUG_LOCAL_BLUR_COARSE, AUG_LOCAL_EMBOSS = 0, 1
 AUG_ELASTIC_MAX_RADIUS = 20
 TF_NONE, TF_SINGLE, TF_PER_FRAME, TF_PER_VIEW = 0, 1, 2, 3
 
-ABI_VERSION = 143   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
+ABI_VERSION = 144   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -142,6 +142,9 @@ PROTOTYPES = {
     "lp_vit_patchify": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "lp_vit_tokens_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "lp_vit_tokens_bwd": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "lp_vit_mv_tokens_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "lp_vit_mv_tokens_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "lp_vit_mv_tokens_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "lp_small_matmul": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "lp_layernorm_fwd": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P]),
     "lp_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
@@ -182,6 +185,8 @@ PROTOTYPES = {
     "lp_f32_vit_patchify": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "lp_f32_vit_tokens_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "lp_f32_vit_tokens_bwd": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "lp_f32_vit_mv_tokens_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "lp_f32_vit_mv_tokens_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "lp_f32_layernorm_fwd": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P]),
     "lp_f32_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "lp_f32_gelu_fwd": (_I, [_P, _Z, _P, _P]),

@@ -1,7 +1,7 @@
 """Checkpoint interchange with the reference.
 
 The reference trains under Lightning, whose ``.ckpt`` is a ``torch.save``d dict: ``state_dict`` (keys ``backbone.{0,1,4..7}.*`` /
-``backbone.vision_encoder.*`` and ``head.upsampling_layers.{1,2}.{weight,bias}``), ``hyper_parameters`` (the constructor arguments
+``backbone.vision_encoder.*`` and ``head.upsampling_layers.{1,2}.{weight,bias}``; the multi-view transformer adds the top-level ``view_embeddings``), ``hyper_parameters`` (the constructor arguments
 kept by ``save_hyperparameters``), ``epoch``, ``global_step``, ``pytorch-lightning_version``, optimizer / scheduler states.  The
 trackers here expose exactly those parameter names and shapes, so weights move in both directions without renaming:
 
@@ -114,8 +114,10 @@ def load_model_from_checkpoint(ckpt_file: str | None, model_class=None, strict: 
     hp["pretrained"] = False  # the weights come from the checkpoint
     hp.pop("backbone_checkpoint", None)
     if model_class is None:
-        from .models import HeatmapTracker, SemiSupervisedHeatmapTracker
-        model_class = SemiSupervisedHeatmapTracker if hp.get("loss_factory_unsupervised") is not None else HeatmapTracker
+        from .models import get_model_class
+        # (num_views is a constructor argument of the multi-view transformer classes only)
+        model_class = get_model_class("heatmap_multiview_transformer" if "num_views" in hp else "heatmap",
+                                      hp.get("loss_factory_unsupervised") is not None)
     model = model_class(**hp)
     model.load_state_dict(ckpt["state_dict"], strict=strict)
     model.current_epoch = int(ckpt.get("epoch", 0))

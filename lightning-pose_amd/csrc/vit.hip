@@ -8,6 +8,7 @@
 // Policy (bf16-mixed): the residual stream, LayerNorm statistics and all reductions are fp32;
 // GEMM operands are bf16.  Every kernel here is an HBM-bound stream or a per-row reduction.
 #include "lp_common.h"
+#include "vit_mv.h"
 
 namespace lp {
 
@@ -568,6 +569,22 @@ extern "C" int lp_vit_tokens_bwd(const float* dx, int B, int Np, int D, void* dp
     hipLaunchKernelGGL(vit_tokens_bwd_kernel, dim3(vit_grid((size_t)(Np + 1) * (D / 8))), dim3(256), 0, (hipStream_t)stream, dx, B, Np, D,
                        (unsigned short*)dpatch_bf16, dpos);
     return launch_status();
+}
+
+extern "C" int lp_vit_mv_tokens_fwd(const void* patch_bf16, const float* pos, const float* view, int B, int V, int Np, int D, float* x,
+                                    lp_stream_t stream) {
+    return lp::mv_tokens_fwd_launch((const unsigned short*)patch_bf16, pos, view, B, V, Np, D, x, (hipStream_t)stream);
+}
+
+extern "C" size_t lp_vit_mv_tokens_bwd_workspace_bytes(int B, int V, int Np, int D) {
+    if (B <= 0 || V <= 0 || Np <= 0 || D <= 0 || D % lp::kMvCols != 0) return 0;
+    return lp::mv_ws_floats(lp::mv_plan(B, V, Np, D), V, Np, D) * sizeof(float);
+}
+
+extern "C" int lp_vit_mv_tokens_bwd(const float* dx, int B, int V, int Np, int D, void* dpatch_bf16, float* dpos, float* dview,
+                                    void* workspace, size_t workspace_bytes, lp_stream_t stream) {
+    return lp::mv_tokens_bwd_launch(dx, B, V, Np, D, (unsigned short*)dpatch_bf16, dpos, dview, (float*)workspace, workspace_bytes,
+                                    (hipStream_t)stream);
 }
 
 extern "C" int lp_small_matmul(const float* w, const float* x, int R, int Q, int D, int transpose_w, int accumulate, float* y,

@@ -5,6 +5,7 @@
 // csrc/fp32.hip does for the ResNet-50 trunk.  Nothing is fused and nothing is tuned: one wave per row, scalar loads, every tensor fp32.
 // The bf16-mixed kernels of vit.hip / attn.hip are the product and the measured path.
 #include "lp_common.h"
+#include "vit_mv.h"
 
 namespace lp {
 
@@ -274,6 +275,17 @@ extern "C" int lp_f32_vit_tokens_fwd(const float* patch, const float* cls, const
     LP_REQUIRE(patch && cls && pos && x && B > 0 && Np > 0 && D > 0);
     hipLaunchKernelGGL(f32_vit_tokens_fwd_kernel, dim3(f32_grid((size_t)B * (Np + 1) * D)), dim3(256), 0, (hipStream_t)stream, patch, cls, pos, B, Np, D, x);
     return launch_status();
+}
+
+// the multi-view token assembly in fp32: the same kernels as the product path (vit_mv.h), patch / dpatch in float
+extern "C" int lp_f32_vit_mv_tokens_fwd(const float* patch, const float* pos, const float* view, int B, int V, int Np, int D, float* x,
+                                        lp_stream_t stream) {
+    return lp::mv_tokens_fwd_launch(patch, pos, view, B, V, Np, D, x, (hipStream_t)stream);
+}
+
+extern "C" int lp_f32_vit_mv_tokens_bwd(const float* dx, int B, int V, int Np, int D, float* dpatch, float* dpos, float* dview, void* workspace,
+                                        size_t workspace_bytes, lp_stream_t stream) {
+    return lp::mv_tokens_bwd_launch(dx, B, V, Np, D, dpatch, dpos, dview, (float*)workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int lp_f32_vit_tokens_bwd(const float* dx, int B, int Np, int D, float* dpatch, float* dpos, lp_stream_t stream) {

@@ -93,6 +93,10 @@ class Plan:
     convs: list[ConvP] = field(default_factory=list)
     bns: list[BNP] = field(default_factory=list)
 
+    def group_ranges(self) -> dict[str, tuple[int, int]]:
+        """optimiser group name -> its range of the flat buffers (optim.FusedAdam)"""
+        return {"backbone": (0, self.n_backbone), "head": (self.n_backbone, self.n_total)}
+
 
 def build_head(feat_channels: int, stride: int, num_keypoints: int, downsample_factor: int, int_channels: int | None = None) -> list[ConvP]:
     """PixelShuffle(2) + n x ConvTranspose2d(k3,s2,p1,op1) of HeatmapHead (reference models/heads/heatmap.py:20-71,186-196):

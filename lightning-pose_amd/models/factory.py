@@ -7,12 +7,15 @@ from typing import Any, get_type_hints
 
 from .base import check_if_semi_supervised
 from .heatmap_tracker import HeatmapTracker, SemiSupervisedHeatmapTracker
+from .heatmap_tracker_multiview import HeatmapTrackerMultiviewTransformer, SemiSupervisedHeatmapTrackerMultiviewTransformer
 
 
 def get_model_class(model_type: str, semi_supervised: bool) -> type:
+    if model_type == "heatmap_multiview_transformer":
+        return SemiSupervisedHeatmapTrackerMultiviewTransformer if semi_supervised else HeatmapTrackerMultiviewTransformer
     if model_type != "heatmap":
         raise NotImplementedError(f"{model_type} is an invalid model_type for a {'semi' if semi_supervised else 'fully'}-supervised "
-                                  "model on the MI355X path (only 'heatmap' is implemented)")
+                                  "model on the MI355X path (only 'heatmap' and 'heatmap_multiview_transformer' are implemented)")
     return SemiSupervisedHeatmapTracker if semi_supervised else HeatmapTracker
 
 
@@ -74,6 +77,9 @@ def get_model(cfg: Any, data_module: Any, loss_factories: dict[str, Any]):
         downsample_factor=int(_get(data, "downsample_factor", 2)),
         backbone_checkpoint=_get(model, "backbone_checkpoint", None),
     )
+    if str(model["model_type"]) == "heatmap_multiview_transformer":   # (reference :285-291)
+        kwargs["num_views"] = len(data["view_names"])
+        kwargs["head"] = str(_get(model, "head", "heatmap_cnn"))
     if semi:
         kwargs["loss_factory_unsupervised"] = loss_factories["unsupervised"]
     net = cls(**kwargs)

@@ -82,10 +82,12 @@ class HeatmapTracker(BaseSupervisedTracker):
             engine_cls = ViTEngine
             if self.precision == "fp32":  # validation mode (vit_engine_fp32.py)
                 from ..vit_engine_fp32 import Fp32ViTEngine as engine_cls
+            engine_kwargs, extra_init = self._vit_engine_extras(hidden)
             self.net = engine_cls(num_keypoints, downsample_factor, device, hidden=hidden, depth=depth, heads=heads, mlp=mlp, patch=patch,
-                                 pretrain_grid=grid)
+                                 pretrain_grid=grid, **engine_kwargs)
             init = vit_seeded_state_dict(hidden, depth, heads, mlp, patch, grid)
             init.update(head_state_dict(self.num_fc_input_features, num_keypoints, self.head.n_layers))
+            init.update(extra_init)
             if pretrained:
                 if checkpoint is None:
                     raise RuntimeError("pretrained=True needs the DINO weights, which cannot be downloaded here; pass "
@@ -134,6 +136,11 @@ class HeatmapTracker(BaseSupervisedTracker):
         self.save_hyperparameters(ignore=["loss_factory", "loss_factory_unsupervised"])
 
     # ------------------------------------------------------------------------------------------------ plumbing
+    def _vit_engine_extras(self, hidden: int) -> tuple[dict, dict]:
+        """(extra constructor arguments of the ViT engine, extra initial tensors by state_dict name): none here; the multi-view
+        transformer selects the engine's multi-view mode and seeds its view embeddings (heatmap_tracker_multiview.py)"""
+        return {}, {}
+
     def _bind_parameters(self) -> None:
         """Expose the engine's flat buffers as nn.Parameters / buffers under the reference's state_dict names."""
         net = self.net

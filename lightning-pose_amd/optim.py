@@ -2,7 +2,8 @@
 
 The reference builds ``torch.optim.Adam(params, lr)`` / ``AdamW`` with two parameter groups
 ``[{"params": backbone, "lr": 0, "name": "backbone"}, {"params": head, "name": "head"}]``
-(lightning_pose/models/base.py:458-479, models/heatmap_tracker.py:193-205); ``UnfreezeBackbone`` then rewrites
+(lightning_pose/models/base.py:458-479, models/heatmap_tracker.py:193-205; the multi-view transformer appends a third,
+``{"params": [view_embeddings], "name": "view_embeddings"}``, models/heatmap_tracker_multiview.py:352-367); ``UnfreezeBackbone`` then rewrites
 ``param_groups[0]["lr"]`` every batch (callbacks.py:126-148) and ``MultiStepLR`` scales both groups per epoch.
 This class keeps exactly that surface (``param_groups``, ``step``, ``zero_grad``, ``state_dict``) but a step is one
 ``lp_adam_step`` launch per group over a contiguous fp32 range, which also emits the bf16 operand copy; the
@@ -28,11 +29,14 @@ class FusedAdam(torch.optim.Optimizer):
         n = engine.plan.n_total
         self.exp_avg = torch.zeros(n, device=engine.device, dtype=torch.float32)
         self.exp_avg_sq = torch.zeros(n, device=engine.device, dtype=torch.float32)
-        # group -> flat range, by the "name" key the reference's callbacks rely on
-        self._ranges = {"backbone": (0, engine.plan.n_backbone), "head": (engine.plan.n_backbone, n)}
+        # group -> flat range, by the "name" key the reference's callbacks rely on; the engine's plan lays the groups out (the multi-view
+        # transformer adds "view_embeddings", reference models/heatmap_tracker_multiview.py:352-367)
+        self._ranges = dict(engine.plan.group_ranges())
         for g in self.param_groups:
             if g.get("name") not in self._ranges:
-                raise ValueError('FusedAdam expects the reference\'s parameter groups named "backbone" and "head"')
+                names = list(self._ranges)
+                expected = " and ".join(f'"{k}"' for k in names) if len(names) == 2 else ", ".join(f'"{k}"' for k in names)
+                raise ValueError(f"FusedAdam expects the reference's parameter groups named {expected}")
             g.setdefault("step", 0)
         self.grad_scale = 1.0  # e.g. 1 / world_size after a SUM all-reduce
 

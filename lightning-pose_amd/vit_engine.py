@@ -73,10 +73,17 @@ class LNP:
 
 
 class ViTPlan:
-    def __init__(self, num_keypoints: int, downsample_factor: int, D: int, depth: int, heads: int, mlp: int, patch: int, n_pos: int):
+    def __init__(self, num_keypoints: int, downsample_factor: int, D: int, depth: int, heads: int, mlp: int, patch: int, n_pos: int,
+                 num_views: int = 0):
         self.D, self.depth, self.heads, self.mlp, self.patch, self.n_pos = D, depth, heads, mlp, patch, n_pos
         pre = "backbone.vision_encoder"
         off = wd = 0
+        # multi-view mode: the (V, D) view embeddings lead the flat buffers.  Their gradient is, with the other embeddings', the LAST to
+        # complete in a backward pass, and grad_progress(offset) promises that G[offset:] is final - a tail position would break that;
+        # in front of the backbone range each of the three optimiser groups is still one contiguous range
+        self.num_views, self.view_off = num_views, off
+        off += num_views * D
+        self.n_view = off
 
         def lin(name, N, K):
             nonlocal off, wd
@@ -118,6 +125,13 @@ class ViTPlan:
         self.n_total, self.n_wd = off, wd
         self.n_running = 0
 
+    def group_ranges(self) -> dict[str, tuple[int, int]]:
+        """optimiser group name -> its range of the flat buffers (optim.FusedAdam)"""
+        ranges = {"backbone": (self.n_view, self.n_backbone), "head": (self.n_backbone, self.n_total)}
+        if self.num_views:
+            ranges["view_embeddings"] = (0, self.n_view)
+        return ranges
+
     def linears(self) -> list[Lin]:
         out = [self.patch_lin]
         for L in self.layers:
@@ -132,12 +146,19 @@ class ViTPlan:
 
 
 class ViTEngine(Engine):
-    """ViT-S/16 defaults = facebook/dino-vits16 (hidden 384, 12 layers, 6 heads, MLP 1536, patch 16, 224-px position table)."""
+    """ViT-S/16 defaults = facebook/dino-vits16 (hidden 384, 12 layers, 6 heads, MLP 1536, patch 16, 224-px position table).
+
+    ``num_views`` = V > 0 selects the multi-view mode (reference models/heatmap_tracker_multiview.py:143-223, ``forward_vit``): the batch is
+    B * V images, row b * V + v view v of sample b; the tokens carry no [CLS] row but a learned ``view_embeddings[v]`` (V, D), and the layers
+    attend over the V * Np tokens of a sample at once (``lp_vit_mv_tokens_fwd`` / ``_bwd``; everything after the token assembly is the same
+    kernels with B sequences of V * Np tokens).  ``cls_token`` and row 0 of the position table stay in the state dict with a zero gradient."""
 
     wgrad_side_stream = False
+    _patch_dtype = torch.bfloat16
+    _token_kernels = ("lp_vit_tokens_fwd", "lp_vit_tokens_bwd", "lp_vit_mv_tokens_fwd", "lp_vit_mv_tokens_bwd")
 
     def __init__(self, num_keypoints: int, downsample_factor: int = 2, device: torch.device | str = "cuda:0", hidden: int = 384,
-                 depth: int = 12, heads: int = 6, mlp: int = 1536, patch: int = 16, pretrain_grid: int = 14):
+                 depth: int = 12, heads: int = 6, mlp: int = 1536, patch: int = 16, pretrain_grid: int = 14, num_views: int = 0):
         self.device = torch.device(device)
         ops.require_device_type(self.device)
         self._lib = _lib.lib()
@@ -145,7 +166,9 @@ class ViTEngine(Engine):
         if hidden % 64 or (hidden // heads) != 64 or mlp % 64:
             raise NotImplementedError("ViT widths must be multiples of 64 with 64-wide heads (ViT-S/B)")
         self.grid0 = pretrain_grid
-        self.plan = ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, 1 + pretrain_grid * pretrain_grid)
+        if num_views < 0:
+            raise ValueError(f"num_views must be positive (0: single-view tokens with [CLS]), got {num_views}")
+        self.plan = ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, 1 + pretrain_grid * pretrain_grid, num_views)
         n, dev = self.plan.n_total, self.device
         self.P = torch.zeros(n, device=dev, dtype=torch.float32)
         self.G = torch.zeros(n, device=dev, dtype=torch.float32)
@@ -169,8 +192,9 @@ class ViTEngine(Engine):
     def _views(self, buf: torch.Tensor) -> dict[str, torch.Tensor]:
         pl, D = self.plan, self.plan.D
         pre = "backbone.vision_encoder"
-        sd = {f"{pre}.embeddings.cls_token": buf[pl.cls_off:pl.cls_off + D].view(1, 1, D),
-              f"{pre}.embeddings.position_embeddings": buf[pl.pos_off:pl.pos_off + pl.n_pos * D].view(1, pl.n_pos, D)}
+        sd = {"view_embeddings": buf[pl.view_off:pl.n_view].view(pl.num_views, D)} if pl.num_views else {}
+        sd[f"{pre}.embeddings.cls_token"] = buf[pl.cls_off:pl.cls_off + D].view(1, 1, D)
+        sd[f"{pre}.embeddings.position_embeddings"] = buf[pl.pos_off:pl.pos_off + pl.n_pos * D].view(1, pl.n_pos, D)
         for l in pl.linears():
             w, b = buf[l.w_off:l.w_off + l.N * l.K], buf[l.b_off:l.b_off + l.N]
             if l.name.endswith("attention.qkv"):  # fused [q; k; v]: three reference parameters share one GEMM weight
@@ -352,6 +376,51 @@ class ViTEngine(Engine):
               "lp_small_matmul")
         return out
 
+    # ------------------------------------------------------------------------------------------------ tokens
+    def _seq(self, parts: list[torch.Tensor], Np: int) -> tuple[int, int, int]:
+        """(sequences, tokens per sequence, ``drop_T`` of the final LayerNorm) for these batches of images with Np patches each"""
+        V = self.plan.num_views
+        B = sum(p_.shape[0] for p_ in parts)
+        if not V:
+            return B, Np + 1, Np + 1            # one sequence per image, [CLS] in front and dropped in front of the head
+        if any(p_.shape[0] % V for p_ in parts):
+            raise ValueError(f"a multi-view batch holds num_views = {V} images per sample, got {[p_.shape[0] for p_ in parts]} images")
+        return B // V, V * Np, 0                # one sequence per sample: the patches of all its views, nothing dropped
+
+    def _tokens_fwd(self, pe: torch.Tensor, pos: torch.Tensor, B: int, Np: int, x: torch.Tensor) -> None:
+        pl, (fwd, _, mv_fwd, _) = self.plan, self._token_kernels
+        if pl.num_views:
+            V = pl.num_views
+            check(getattr(self._lib, mv_fwd)(_p(pe), _p(pos), _p(self.P[pl.view_off:]), B // V, V, Np, pl.D, _p(x), ops._stream()), mv_fwd)
+        else:
+            check(getattr(self._lib, fwd)(_p(pe), _p(self.P[pl.cls_off:]), _p(pos), B, Np, pl.D, _p(x), ops._stream()), fwd)
+
+    def _tokens_bwd(self, dx: torch.Tensor, B: int, Np: int, gh: int, gw: int) -> torch.Tensor:
+        """Gradient of the token assembly: returns d(patch embeddings) and accumulates the [CLS] token's / the view embeddings' and the
+        position table's gradients (through the adjoint of its interpolation) into G"""
+        pl, D, dev = self.plan, self.plan.D, self.device
+        _, bwd, _, mv_bwd = self._token_kernels
+        dpatch = torch.empty(B * Np, D, device=dev, dtype=self._patch_dtype)
+        dpos = torch.empty(Np + 1, D, device=dev, dtype=torch.float32)
+        gpos = self.G[pl.pos_off:pl.pos_off + pl.n_pos * D].view(pl.n_pos, D)
+        if pl.num_views:   # no [CLS] row: cls_token and gpos[0] keep their zero gradient
+            V = pl.num_views
+            dview = torch.empty(V, D, device=dev, dtype=torch.float32)
+            nws = int(self._lib.lp_vit_mv_tokens_bwd_workspace_bytes(B // V, V, Np, D))
+            ws = torch.empty(max(nws, 4) // 4, device=dev, dtype=torch.float32)
+            check(getattr(self._lib, mv_bwd)(_p(dx), B // V, V, Np, D, _p(dpatch), _p(dpos), _p(dview), _p(ws), nws, ops._stream()), mv_bwd)
+            self.G[pl.view_off:pl.n_view] += dview.view(-1)
+        else:
+            check(getattr(self._lib, bwd)(_p(dx), B, Np, D, _p(dpatch), _p(dpos), ops._stream()), bwd)
+            self.G[pl.cls_off:pl.cls_off + D] += dpos[0]
+            gpos[0] += dpos[0]
+        if gh == self.grid0 and gw == self.grid0:
+            gpos[1:] += dpos[1:]
+        else:
+            check(self._lib.lp_small_matmul(_p(self._interp[(gh, gw)]), _p(dpos[1:]), Np, pl.n_pos - 1, D, 1, 1, _p(gpos[1:]), ops._stream()),
+                  "lp_small_matmul(adjoint)")
+        return dpatch
+
     # ------------------------------------------------------------------------------------------------ forward
     def can_segment(self, n0: int, H: int, W: int) -> bool:
         """no batch statistics anywhere (LayerNorm is per token): two batches of equally sized images always share one pass"""
@@ -382,12 +451,13 @@ class ViTEngine(Engine):
         if H % pt or W % pt:
             raise ValueError(f"image size must be a multiple of the patch size {pt}, got {H}x{W}")
         gh, gw = H // pt, W // pt
-        Np, Tn = gh * gw, gh * gw + 1
-        M, Tp = B * Tn, -(-Tn // 64) * 64
+        Np = gh * gw
+        Bs, Tn, drop_T = self._seq(parts, Np)   # (B images; the layers see Bs sequences of Tn tokens)
+        M, Tp = Bs * Tn, -(-Tn // 64) * 64
         tp = Tape()
         T = tp.t
         dev = self.device
-        self._wg_shape = (B, Tn)
+        self._wg_shape = (Bs, Tn)
 
         patches = torch.empty(B * Np, 3 * pt * pt, device=dev, dtype=torch.bfloat16)
         i0 = 0
@@ -397,7 +467,7 @@ class ViTEngine(Engine):
         pe = self._linear(patches, pl.patch_lin, B * Np)
         x = torch.empty(M, D, device=dev, dtype=torch.float32)
         pos = self._pos(gh, gw)  # (kept alive across the launch)
-        check(self._lib.lp_vit_tokens_fwd(_p(pe), _p(self.P[pl.cls_off:]), _p(pos), B, Np, D, _p(x), ops._stream()), "lp_vit_tokens_fwd")
+        self._tokens_fwd(pe, pos, B, Np, x)
         if keep:
             T["patches"] = patches
         delta = None
@@ -408,12 +478,12 @@ class ViTEngine(Engine):
             qkv = self._linear(y1, L["qkv"], M)
             # P = softmax(Q K^T / 8) (bf16, row pitch Tp, pad columns zero; kept for the backward pass) and attn = P V in one kernel:
             # the scores themselves never reach memory
-            S = torch.empty(B * nh * Tn, Tp, device=dev, dtype=torch.bfloat16) if keep else None
+            S = torch.empty(Bs * nh * Tn, Tp, device=dev, dtype=torch.bfloat16) if keep else None
             attn = torch.empty(M, D, device=dev, dtype=torch.bfloat16)
             # scores + probabilities x values: 2 products of B * nh * Tn * Tn * (D / nh) MACs; the training pass computes the scores twice
-            self._timed("attn_fwd_kernel", 4.0 * B * Tn * Tn * D, lambda: check(self._lib.lp_attn_fwd(
-                _p(qkv), qs, D, 2 * D, B, nh, Tn, scale, _p(S), Tp, _p(attn), D, ops._stream()), "lp_attn_fwd"),
-                nbytes=2.0 * (3 * B * Tn * D + B * Tn * D) + (2.0 * B * nh * Tn * Tp if S is not None else 0.0))
+            self._timed("attn_fwd_kernel", 4.0 * Bs * Tn * Tn * D, lambda: check(self._lib.lp_attn_fwd(
+                _p(qkv), qs, D, 2 * D, Bs, nh, Tn, scale, _p(S), Tp, _p(attn), D, ops._stream()), "lp_attn_fwd"),
+                nbytes=2.0 * (3 * Bs * Tn * D + Bs * Tn * D) + (2.0 * Bs * nh * Tn * Tp if S is not None else 0.0))
             proj = self._linear(attn, L["proj"], M)
             x_in = x
             y2, m2, r2, x = self._ln(x, proj, L["ln2"], M)
@@ -423,11 +493,11 @@ class ViTEngine(Engine):
                 for nm, v in (("x_in", x_in), ("m1", m1), ("r1", r1), ("y1", y1), ("qkv", qkv), ("P", S), ("attn", attn), ("x_mid", x),
                               ("m2", m2), ("r2", r2), ("y2", y2), ("h1", h1), ("a1", a1)):
                     T[f"l{i}.{nm}"] = v
-        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=Tn)
+        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T)
         if keep:
             T["x_last"], T["mf"], T["rf"] = x, mf, rf
         heat = self._head_forward(feat.view(B, gh, gw, D), B, gh, gw, T if keep else {})
-        tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training)
+        tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training, seq=(Bs, Tn, drop_T))
         return heat, tp
 
     # ------------------------------------------------------------------------------------------------ backward
@@ -435,10 +505,11 @@ class ViTEngine(Engine):
         T, pl = tp.t, self.plan
         B, gh, gw = tp.meta["B"], tp.meta["gh"], tp.meta["gw"]
         D, nh = pl.D, pl.heads
-        Np, Tn = gh * gw, gh * gw + 1
-        M, Tp = B * Tn, -(-Tn // 64) * 64
+        Np = gh * gw
+        Bs, Tn, drop_T = tp.meta["seq"]
+        M, Tp = Bs * Tn, -(-Tn // 64) * 64
         dev = self.device
-        self._wg_shape = (B, Tn)
+        self._wg_shape = (Bs, Tn)
         scale = 1.0 / math.sqrt(D // nh)
         qs = 3 * D
 
@@ -452,7 +523,7 @@ class ViTEngine(Engine):
         fuse_bias = os.environ.get("LP_VIT_BIAS_FUSED", "1") != "0"
         fuse_gelu = os.environ.get("LP_VIT_GELU_FUSED", "1") != "0"   # (0: A/B runs - lp_gemm_nt, then lp_gelu_bwd_colsum)
         bsum = (lambda lin: self.G[lin.b_off:lin.b_off + lin.N]) if fuse_bias else (lambda lin: None)
-        dx16 = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=Tn, want_bf16=True, colsum=bsum(pl.layers[-1]["fc2"]))
+        dx16 = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, colsum=bsum(pl.layers[-1]["fc2"]))
 
         for i in range(pl.depth - 1, -1, -1):
             L = pl.layers[i]
@@ -482,21 +553,21 @@ class ViTEngine(Engine):
             d_attn = self._linear_bwd(L["proj"], t("attn"), dproj, M)
             qkv, Pm = t("qkv"), t("P")
             dqkv = torch.empty(M, qs, device=dev, dtype=torch.bfloat16)
-            zP = (nh * Tn * Tp, Tn * Tp)       # batch strides of a [B][nh][Tn][Tp] tensor
+            zP = (nh * Tn * Tp, Tn * Tp)       # batch strides of a [Bs][nh][Tn][Tp] tensor
             zT = (nh * 64 * Tp, 64 * Tp)       # ... of a [B][nh][64][Tp] transposed head slice
             # D = rowsum(dO o O) (== rowsum(dP o P) because O = P V), then ONE pass over the stored probabilities leaves
             # dS = scale * P o (dO V^T - D), dV = P^T dO and dK = dS^T Q (dP never exists; P and dS are touched once each here)
             drow = torch.empty(M, nh, device=dev, dtype=torch.float32)
             check(self._lib.lp_attn_rowdot(_p(d_attn), _p(t("attn")), M, nh, D, _p(drow), ops._stream()), "lp_attn_rowdot")
-            dS = torch.empty(B * nh * Tn, Tp, device=dev, dtype=torch.bfloat16)
+            dS = torch.empty(Bs * nh * Tn, Tp, device=dev, dtype=torch.bfloat16)
             # dP = dO V^T, dV = P^T dO, dK = dS^T Q: 3 products of B * Tn * Tn * D MACs
-            self._timed("attn_bwd_kv_kernel", 6.0 * B * Tn * Tn * D, lambda: check(self._lib.lp_attn_bwd_kv(
-                _p(qkv), qs, 2 * D, _p(d_attn), D, _p(Pm), Tp, _p(drow), B, nh, Tn, scale, _p(dS), _p(dqkv), qs, D, 2 * D, ops._stream()),
-                "lp_attn_bwd_kv"), nbytes=2.0 * (2 * B * nh * Tn * Tp + 6 * B * Tn * D))
+            self._timed("attn_bwd_kv_kernel", 6.0 * Bs * Tn * Tn * D, lambda: check(self._lib.lp_attn_bwd_kv(
+                _p(qkv), qs, 2 * D, _p(d_attn), D, _p(Pm), Tp, _p(drow), Bs, nh, Tn, scale, _p(dS), _p(dqkv), qs, D, 2 * D, ops._stream()),
+                "lp_attn_bwd_kv"), nbytes=2.0 * (2 * Bs * nh * Tn * Tp + 6 * Bs * Tn * D))
             # dQ = dS K
-            tmpT = torch.empty(B * nh * 64, Tp, device=dev, dtype=torch.bfloat16)      # a transposed [64][Tp] head slice
-            self._transpose(qkv[:, D:].data_ptr(), Tn, 64, qs, Tn * qs, 64, tmpT, Tp, *zT, B, nh)
-            self._gemm(_p(dS), Tp, _p(tmpT), Tp, Tn, 64, Tp, dqkv, qs, batch=(B, nh, *zP, *zT, Tn * qs, 64))
+            tmpT = torch.empty(Bs * nh * 64, Tp, device=dev, dtype=torch.bfloat16)      # a transposed [64][Tp] head slice
+            self._transpose(qkv[:, D:].data_ptr(), Tn, 64, qs, Tn * qs, 64, tmpT, Tp, *zT, Bs, nh)
+            self._gemm(_p(dS), Tp, _p(tmpT), Tp, Tn, 64, Tp, dqkv, qs, batch=(Bs, nh, *zP, *zT, Tn * qs, 64))
             if trace is not None:
                 trace[f"l{i}.dqkv"] = dqkv
             d_y1 = self._linear_bwd(L["qkv"], t("y1"), dqkv, M)
@@ -507,17 +578,7 @@ class ViTEngine(Engine):
         if trace is not None:
             trace["tokens.dx"] = dx
         # ---- embeddings
-        dpatch = torch.empty(B * Np, D, device=dev, dtype=torch.bfloat16)
-        dpos = torch.empty(Tn, D, device=dev, dtype=torch.float32)
-        check(self._lib.lp_vit_tokens_bwd(_p(dx), B, Np, D, _p(dpatch), _p(dpos), ops._stream()), "lp_vit_tokens_bwd")
-        self.G[pl.cls_off:pl.cls_off + D] += dpos[0]
-        gpos = self.G[pl.pos_off:pl.pos_off + pl.n_pos * D].view(pl.n_pos, D)
-        gpos[0] += dpos[0]
-        if gh == self.grid0 and gw == self.grid0:
-            gpos[1:] += dpos[1:]
-        else:
-            check(self._lib.lp_small_matmul(_p(self._interp[(gh, gw)]), _p(dpos[1:]), Np, pl.n_pos - 1, D, 1, 1, _p(gpos[1:]), ops._stream()),
-                  "lp_small_matmul(adjoint)")
+        dpatch = self._tokens_bwd(dx, B, Np, gh, gw)
         self._wg_shape = (B, Np)
         self._linear_bwd(pl.patch_lin, T["patches"], dpatch, B * Np, need_dx=False)
         self._join_side_stream()

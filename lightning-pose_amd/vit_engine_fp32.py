@@ -27,6 +27,8 @@ class Fp32ViTEngine(ViTEngine):
     :class:`Fp32Engine`).  VALIDATION path: untuned, selected with ``precision="fp32"`` / ``LP_PRECISION=fp32``."""
 
     precision = "fp32"
+    _patch_dtype = torch.float32
+    _token_kernels = ("lp_f32_vit_tokens_fwd", "lp_f32_vit_tokens_bwd", "lp_f32_vit_mv_tokens_fwd", "lp_f32_vit_mv_tokens_bwd")
     _f32 = Fp32Engine._f32
     _wdims = staticmethod(Fp32Engine._wdims)
     _wg = Fp32Engine._wg
@@ -87,8 +89,9 @@ class Fp32ViTEngine(ViTEngine):
         if H % pt or W % pt:
             raise ValueError(f"image size must be a multiple of the patch size {pt}, got {H}x{W}")
         gh, gw = H // pt, W // pt
-        Np, Tn = gh * gw, gh * gw + 1
-        M = B * Tn
+        Np = gh * gw
+        Bs, Tn, drop_T = self._seq(parts, Np)   # (B images; the layers see Bs sequences of Tn tokens)
+        M = Bs * Tn
         tp = Tape()
         T = tp.t
         patches = self._f32(B * Np, 3 * pt * pt)
@@ -99,7 +102,7 @@ class Fp32ViTEngine(ViTEngine):
         pe = self._linear(patches, pl.patch_lin, B * Np)
         x = self._f32(M, D)
         pos = self._pos(gh, gw)
-        check(self._lib.lp_f32_vit_tokens_fwd(_p(pe), _p(self.P[pl.cls_off:]), _p(pos), B, Np, D, _p(x), ops._stream()), "lp_f32_vit_tokens_fwd")
+        self._tokens_fwd(pe, pos, B, Np, x)
         T["patches"] = patches
         delta = None
         scale = 1.0 / math.sqrt(D // nh)
@@ -107,9 +110,9 @@ class Fp32ViTEngine(ViTEngine):
         for i, L in enumerate(pl.layers):
             y1, m1, r1, x = self._ln(x, delta, L["ln1"], M)
             qkv = self._linear(y1, L["qkv"], M)
-            Pm = self._f32(B * nh * Tn, Tn)
+            Pm = self._f32(Bs * nh * Tn, Tn)
             attn = self._f32(M, D)
-            check(self._lib.lp_f32_attn_fwd(_p(qkv), qs, D, 2 * D, B, nh, Tn, scale, _p(Pm), _p(attn), D, ops._stream()), "lp_f32_attn_fwd")
+            check(self._lib.lp_f32_attn_fwd(_p(qkv), qs, D, 2 * D, Bs, nh, Tn, scale, _p(Pm), _p(attn), D, ops._stream()), "lp_f32_attn_fwd")
             proj = self._linear(attn, L["proj"], M)
             x_in = x
             y2, m2, r2, x = self._ln(x, proj, L["ln2"], M)
@@ -121,23 +124,24 @@ class Fp32ViTEngine(ViTEngine):
                 for nm, v in (("x_in", x_in), ("m1", m1), ("r1", r1), ("y1", y1), ("qkv", qkv), ("P", Pm), ("attn", attn), ("x_mid", x),
                               ("m2", m2), ("r2", r2), ("y2", y2), ("h1", h1), ("a1", a1)):
                     T[f"l{i}.{nm}"] = v
-        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=Tn)
+        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T)
         T["x_last"], T["mf"], T["rf"] = x, mf, rf
         heat = self._head_forward(feat.view(B, gh, gw, D), B, gh, gw, T)
-        tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training)
+        tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training, seq=(Bs, Tn, drop_T))
         return heat, tp
 
     def backward(self, tp: Tape, g_heat: torch.Tensor, trace: dict | None = None) -> None:
         T, pl = tp.t, self.plan
         B, gh, gw = tp.meta["B"], tp.meta["gh"], tp.meta["gw"]
         D, nh = pl.D, pl.heads
-        Np, Tn = gh * gw, gh * gw + 1
-        M = B * Tn
+        Np = gh * gw
+        Bs, Tn, drop_T = tp.meta["seq"]
+        M = Bs * Tn
         scale = 1.0 / math.sqrt(D // nh)
         qs = 3 * D
         d_feat = self._head_backward(T, B, g_heat).contiguous()            # (B, gh, gw, D) fp32
         dx = torch.zeros(M, D, device=self.device, dtype=torch.float32)   # gradient of the residual stream
-        dcur = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=Tn, want_bf16=True)
+        dcur = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True)
         for i in range(pl.depth - 1, -1, -1):
             L = pl.layers[i]
             t = lambda nm: T[f"l{i}.{nm}"]  # noqa: E731
@@ -150,8 +154,8 @@ class Fp32ViTEngine(ViTEngine):
             dcur = self._ln_bwd(d_y2, t("x_mid"), t("m2"), t("r2"), L["ln2"], M, dx, want_bf16=True)
             d_attn = self._linear_bwd(L["proj"], t("attn"), dcur, M)
             dqkv = self._f32(M, qs)
-            dS = self._f32(B * nh * Tn, Tn)
-            check(self._lib.lp_f32_attn_bwd(_p(t("qkv")), qs, D, 2 * D, _p(d_attn), D, _p(t("P")), B, nh, Tn, scale, _p(dS), _p(dqkv), qs,
+            dS = self._f32(Bs * nh * Tn, Tn)
+            check(self._lib.lp_f32_attn_bwd(_p(t("qkv")), qs, D, 2 * D, _p(d_attn), D, _p(t("P")), Bs, nh, Tn, scale, _p(dS), _p(dqkv), qs,
                                             ops._stream()), "lp_f32_attn_bwd")
             if trace is not None:
                 trace[f"l{i}.dqkv"] = dqkv
@@ -159,15 +163,5 @@ class Fp32ViTEngine(ViTEngine):
             dcur = self._ln_bwd(d_y1, t("x_in"), t("m1"), t("r1"), L["ln1"], M, dx, want_bf16=i > 0)
         if trace is not None:
             trace["tokens.dx"] = dx
-        dpatch = self._f32(B * Np, D)
-        dpos = self._f32(Tn, D)
-        check(self._lib.lp_f32_vit_tokens_bwd(_p(dx), B, Np, D, _p(dpatch), _p(dpos), ops._stream()), "lp_f32_vit_tokens_bwd")
-        self.G[pl.cls_off:pl.cls_off + D] += dpos[0]
-        gpos = self.G[pl.pos_off:pl.pos_off + pl.n_pos * D].view(pl.n_pos, D)
-        gpos[0] += dpos[0]
-        if gh == self.grid0 and gw == self.grid0:
-            gpos[1:] += dpos[1:]
-        else:
-            check(self._lib.lp_small_matmul(_p(self._interp[(gh, gw)]), _p(dpos[1:]), Np, pl.n_pos - 1, D, 1, 1, _p(gpos[1:]), ops._stream()),
-                  "lp_small_matmul(adjoint)")
+        dpatch = self._tokens_bwd(dx, B, Np, gh, gw)
         self._linear_bwd(pl.patch_lin, T["patches"], dpatch, B * Np, need_dx=False)
