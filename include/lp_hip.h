@@ -207,6 +207,7 @@ typedef struct lp_conv_geom {
 #define LP_CONV_KERNEL_PIPE_HALO 4 /* conv_pipe_kernel<..., HALO>: 3x3 / stride 1, the input neighbourhood staged once (LP_CONV_HALO=0 disables) */
 /* (6, 7: round 5's producer / consumer kernel conv_spec_kernel - measured not faster, retired in round 6: profiles/retired/r05_conv_spec.h.txt) */
 #define LP_CONV_KERNEL_STEM_WGRAD_NB 8 /* stem_wgrad_nb_kernel: the stem's weight gradient from a staged input neighbourhood (LP_STEM_WGRAD_NB=0 disables) */
+#define LP_CONV_KERNEL_WGRAD_NB 9 /* conv_wgrad_nb_kernel: 3x3 / stride 1 weight gradient, input staged once for all nine taps (LP_WGRAD_NB=0 disables) */
 #define LP_CONV_KERNEL_RES2D 5     /* conv_res2d_kernel: 3x3 / stride 1, 64 -> 64 channels, 16 x 16 tiles, filter resident in LDS (LP_CONV_RES2D=0 disables) */
 int lp_conv_last_kernel(void);
 

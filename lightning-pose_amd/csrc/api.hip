@@ -20,6 +20,7 @@ static LpSwitches read_switches() {
     s.infer_pipe = env_int("LP_INFER_PIPE", 1);     // 0: lp_conv_fwd_act on conv_igemm_kernel<infer>
     s.gemm_pipe = env_int("LP_GEMM_PIPE", 1);       // 0: the Linear layers on conv_igemm_kernel
     s.wgrad_pipe = env_int("LP_WGRAD_PIPE", 1);     // 0: weight gradients on conv_wgrad_kernel; 2: the pipelined kernel wherever it can run
+    s.wgrad_nb = env_int("LP_WGRAD_NB", 1);         // 0: the 3x3 / stride 1 weight gradients on conv_wgrad_pipe_kernel / conv_wgrad_kernel (LP_WGRAD_PIPE=1 only)
     s.stem_2d = env_int("LP_STEM_2D", 1);           // 0: the stem on conv_igemm_kernel<64, stem>
     s.stem_wgrad_nb = env_int("LP_STEM_WGRAD_NB", 1);   // 0: the stem's weight gradient on conv_wgrad_kernel<64, stem>
     s.pool_v2 = env_int("LP_POOL_V2", 1);           // 0: the stem's pool backward on the first kernel

@@ -1232,6 +1232,7 @@ static int launch_pipe_dgrad(int kind, const void* x, const void* w, const ConvG
 
 }  // namespace lp
 #include "conv_stem_wgrad.h"
+#include "conv_wgrad_nb.h"
 namespace lp {
 
 constexpr int kWgradWgs = 512;  // workgroups per weight-gradient launch (tiles x pixel slices)
@@ -1336,6 +1337,69 @@ static void launch_wgrad_pipe(const WgradPipePlan& p, const void* x, const void*
                            (const unsigned short*)qb, pa_bytes, qb_bytes, wg, M, tiles, p.tiles_b, p.per, dhw, dwo, ws);
         hipLaunchKernelGGL((wgrad_pipe_reduce_kernel<64>), dim3(tiles * 256 * 64 / 64), dim3(256), 0, st, ws, p.split, tiles, p.tiles_b, p.Ka,
                            p.Cb, sa, sb, dw);
+    }
+}
+
+// ---- 3x3 / stride 1 / pad 1 weight gradient from a staged neighbourhood (conv_wgrad_nb.h): one workgroup per (64 ci, bn co, slice of the
+// padded raster), ONE resident round (a workgroup's partial tile is 9 x 64 x bn fp32: more slices than CUs only add workspace traffic)
+struct WgradNbPlan {
+    bool ok;
+    int bn, kh, tiles_a, tiles_b, split, per, PT, lead;
+    size_t ws_floats;
+};
+
+static WgradNbPlan plan_wgrad_nb(const ConvGeom& g, int split_hint) {
+    WgradNbPlan p{};
+    if (g.R != 3 || g.S != 3 || g.stride != 1 || g.pad != 1 || g.Hi != g.Ho || g.Wi != g.Wo || g.Ci % 64 != 0 || g.Co % 64 != 0) return p;
+    if (g.Wi > 126) return p;   // the x window holds 2 lead + 3 chunks of 64 raster rows, lead = 1 + (W + 1) / 64 <= 2
+    const long long pt = (long long)g.B * (g.Hi + 1) * (g.Wi + 1);
+    if (pt + 64 * 8 >= (1LL << 31)) return p;
+    p.PT = (int)pt;
+    p.lead = 1 + (g.Wi + 1) / 64;
+    p.bn = g.Co % 128 == 0 ? 128 : 64;
+    p.kh = p.bn == 64 ? 2 : 1;
+    p.tiles_a = g.Ci / 64;
+    p.tiles_b = g.Co / p.bn;
+    const int tiles = p.tiles_a * p.tiles_b;
+    const int ksteps = (p.PT + kBK - 1) / kBK;
+    int split = split_hint;
+    if (split <= 0) {
+        // in microseconds at the MFMA rate: a K step is 9 x 4 x bn/16 MFMAs per CU; a workgroup's partial tile (295 KB for either bn) takes
+        // ~15 us to leave at a 1/256 share of the memory rate, and the reduction reads it back
+        const int cus = pipe_max_wgs();
+        const double step_us = 0.96 * p.bn / 128.0;
+        double best = 1e30;
+        for (int s = 1; s <= ksteps && s * tiles <= 2 * cus; ++s) {
+            const double rounds = (double)((tiles * s + cus - 1) / cus), per = (double)((ksteps + s - 1) / s);
+            const double cost = rounds * (per * step_us + 15.0) + 0.06 * s * tiles;
+            if (cost < best) best = cost, split = s;
+        }
+        if (split <= 0) split = 1;
+    }
+    if (split > ksteps) split = ksteps;
+    if (split < 1) split = 1;
+    if (split > 65535) split = 65535;
+    p.per = ((ksteps + split - 1) / split) * kBK;
+    p.split = (p.PT + p.per - 1) / p.per;
+    p.ws_floats = (size_t)p.split * p.kh * tiles * 9 * 64 * p.bn;
+    p.ok = true;
+    return p;
+}
+
+static void launch_wgrad_nb(const WgradNbPlan& p, const void* x, const void* dy, const ConvGeom& g, float* dw, float* ws, hipStream_t st) {
+    const unsigned x_bytes = (unsigned)(2ull * g.B * g.Hi * g.Wi * g.Ci), dy_bytes = (unsigned)(2ull * g.B * g.Ho * g.Wo * g.Co);
+    const WgradNbGeom ng{g.B, g.Hi, g.Wi, g.Ci, g.Co, p.PT, p.lead};
+    const int tiles = p.tiles_a * p.tiles_b;
+    const FastDiv dwp = make_fastdiv(g.Wi + 1), dhp = make_fastdiv(g.Hi + 1);
+    g_last_conv_kernel = LP_CONV_KERNEL_WGRAD_NB;
+    if (p.bn == 128) {
+        hipLaunchKernelGGL((conv_wgrad_nb_kernel<128>), dim3(tiles * p.split), dim3(512), 0, st, (const unsigned short*)x, (const unsigned short*)dy,
+                           x_bytes, dy_bytes, ng, tiles, p.tiles_b, p.per, dwp, dhp, ws);
+        hipLaunchKernelGGL((wgrad_nb_reduce_kernel<128>), dim3(tiles * 9 * 128), dim3(256), 0, st, ws, p.split * p.kh, tiles, p.tiles_b, g.Ci, dw);
+    } else {
+        hipLaunchKernelGGL((conv_wgrad_nb_kernel<64>), dim3(tiles * p.split), dim3(512), 0, st, (const unsigned short*)x, (const unsigned short*)dy,
+                           x_bytes, dy_bytes, ng, tiles, p.tiles_b, p.per, dwp, dhp, ws);
+        hipLaunchKernelGGL((wgrad_nb_reduce_kernel<64>), dim3(tiles * 9 * 64), dim3(256), 0, st, ws, p.split * p.kh, tiles, p.tiles_b, g.Ci, dw);
     }
 }
 
@@ -1680,6 +1744,8 @@ extern "C" size_t lp_conv_wgrad_workspace_bytes(const lp_conv_geom* geom, int sp
     if (!stem) {   // either kernel may take the launch (LP_CONV_PIPE): room for both plans
         const WgradPipePlan pp = plan_wgrad_pipe(g, split_hint, true);   // (the forced plan is the larger one)
         if (pp.ok && pp.ws_floats > fl) fl = pp.ws_floats;
+        const WgradNbPlan np = plan_wgrad_nb(g, split_hint);
+        if (np.ok && np.ws_floats > fl) fl = np.ws_floats;
     }
     return fl * sizeof(float);
 }
@@ -1700,6 +1766,13 @@ static int conv_wgrad_impl(const void* x, const void* dy, const lp_conv_geom* ge
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     const int wpe = lp_switches().wgrad_pipe;   // (LP_WGRAD_PIPE, A/B: 0 keeps the weight gradients on conv_wgrad_kernel; 2 = wherever it can run)
+    if (!dbias && conv_pipe_enabled() && wpe == 1 && lp_switches().wgrad_nb != 0) {   // (LP_WGRAD_PIPE=0 / 2 keep their meaning: the A/B arms)
+        const WgradNbPlan np = plan_wgrad_nb(g, split_hint);
+        if (np.ok && workspace_bytes >= np.ws_floats * sizeof(float)) {
+            launch_wgrad_nb(np, x, dy, g, dw, ws, st);
+            return launch_status();
+        }
+    }
     if (!dbias && conv_pipe_enabled() && wpe != 0) {
         const WgradPipePlan pp = plan_wgrad_pipe(g, split_hint, wpe == 2);
         if (pp.ok && workspace_bytes >= pp.ws_floats * sizeof(float)) {

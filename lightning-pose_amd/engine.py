@@ -289,6 +289,8 @@ class Engine:
                 tag = tag.replace("conv_igemm_kernel<64,", "conv_res2d_kernel<").replace("conv_igemm_kernel<64>", "conv_res2d_kernel<fwd>")
             elif k == _lib.CONV_KERNEL_WGRAD_PIPE:
                 tag = tag.replace("conv_wgrad_kernel", "conv_wgrad_pipe_kernel")
+            elif k == _lib.CONV_KERNEL_WGRAD_NB:
+                tag = tag.replace("conv_wgrad_kernel", "conv_wgrad_nb_kernel")
         self.profile.append((tag, flops, e0, e1, nbytes, layer))
         return out
 
