@@ -336,7 +336,10 @@ int lp_stem_fwd_bn(const void* x4, const void* w, const lp_conv_geom* geom, void
 int lp_conv_dgrad_bn(const void* dy, const void* wd, const lp_conv_geom* geom, const void* addend, const void* relu_mask,
                      void* dx_bf16, const lp_bn_fuse* bn, lp_stream_t stream);
 /* dw: fp32 [Co][R][S][Ci], accumulated into (zero it first); split_hint <= 0 picks the pixel split.  The pixel slices leave
- * partial tiles in `workspace` (lp_conv_wgrad_workspace_bytes) and a second kernel sums them in a fixed order: deterministic. */
+ * partial tiles in `workspace` (lp_conv_wgrad_workspace_bytes) and a second kernel sums them in a fixed order: deterministic.
+ * lp_conv_wgrad_workspace_bytes(geom, split_hint) suffices for the same geom and split_hint whichever kernel the LP_* switches route
+ * the launch to.  A workspace smaller than the routed kernel's plan needs is LP_ERR_ARGUMENT, returned before anything is launched
+ * (lp_conv_wgrad, lp_conv_wgrad_bias, lp_stem_wgrad): the library does not fall back to a slower kernel with a smaller plan. */
 size_t lp_conv_wgrad_workspace_bytes(const lp_conv_geom* geom, int split_hint);
 int lp_conv_wgrad(const void* x, const void* dy, const lp_conv_geom* geom, float* dw, int split_hint, void* workspace,
                   size_t workspace_bytes, lp_stream_t stream);

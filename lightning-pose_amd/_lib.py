@@ -51,9 +51,9 @@ class GemmBatch(C.Structure):
 
 
 HM_MSE, HM_KL, HM_JS = 0, 1, 2
-CONV_KERNEL_IGEMM, CONV_KERNEL_PIPE, CONV_KERNEL_WGRAD, CONV_KERNEL_WGRAD_PIPE, CONV_KERNEL_PIPE_HALO, CONV_KERNEL_RES2D = 0, 1, 2, 3, 4, 5   # lp_conv_last_kernel()
-CONV_KERNEL_STEM_WGRAD_NB = 8
-CONV_KERNEL_WGRAD_NB = 9
+# lp_conv_last_kernel() ids 0 .. 9 (include/lp_hip.h: LP_CONV_KERNEL_*; 6 and 7 were conv_spec_kernel's, retired in round 6)
+(CONV_KERNEL_IGEMM, CONV_KERNEL_PIPE, CONV_KERNEL_WGRAD, CONV_KERNEL_WGRAD_PIPE, CONV_KERNEL_PIPE_HALO, CONV_KERNEL_RES2D, _CONV_KERNEL_6,
+ _CONV_KERNEL_7, CONV_KERNEL_STEM_WGRAD_NB, CONV_KERNEL_WGRAD_NB) = range(10)
 BORDER_RENORM, BORDER_CLAMP = 0, 1
 # include/lp_hip.h: LP_AUG_* flags, Philox op numbers, lp_labelaug_local's `which`
 AUG_GEOM, AUG_BLUR, AUG_DROPOUT, AUG_DROP_PER_CHANNEL, AUG_SALT, AUG_PEPPER = 1, 2, 4, 8, 16, 32

@@ -1237,42 +1237,68 @@ namespace lp {
 
 constexpr int kWgradWgs = 512;  // workgroups per weight-gradient launch (tiles x pixel slices)
 
-struct WgradPlan {
-    int tj, tn, split, per;
-    bool wide;
-    size_t ws_floats;
+// ---- weight-gradient dispatch: wgrad_candidates() lists the plans a geometry admits (shape rules), route_wgrad() picks the one the
+// switches allow (switch rules); lp_conv_wgrad_workspace_bytes, lp_conv_wgrad[_bias] and lp_stem_wgrad all go through the two.
+struct WgradRoute {
+    bool ok;                    // the geometry admits this kernel
+    int kernel;                 // LP_CONV_KERNEL_WGRAD, _WGRAD_PIPE, _WGRAD_NB or _STEM_WGRAD_NB
+    int split, per;             // pixel slices, and the pixels (whole K steps) of one
+    size_t ws_floats;           // the partial tiles of all slices
+    int bn, tiles_a, tiles_b;   // tile width (64 | 128) and tile counts: a = the (r, s, ci) side, b = co (conv_wgrad_pipe_kernel: see swap)
+    bool swap, tuned;           // conv_wgrad_pipe_kernel: a = co, b = ci; passes the two performance rules (LP_WGRAD_PIPE=2 does not ask)
+    int Ka, Cb;                 // conv_wgrad_pipe_kernel: extents of its a and b sides
+    int kh, PT, lead;           // conv_wgrad_nb_kernel: K halves per slice, positions of the padded raster, lead chunks of the x window
 };
 
-static WgradPlan plan_wgrad(int M, int Kw, int Co, int split_hint, int target_wgs) {
-    WgradPlan p;
-    p.tj = (Kw + kBM - 1) / kBM;
-    p.wide = Co > 64;
-    p.tn = p.wide ? (Co + 127) / 128 : 1;
-    // the chip holds 512 of these workgroups at once (2 per CU, LDS-bound): aim just below a whole number of rounds
-    int split = split_hint > 0 ? split_hint : target_wgs / (p.tj * p.tn);
-    const int ksteps = (M + kBK - 1) / kBK;
-    if (split > ksteps) split = ksteps;
+// `units` pixels (M, or positions of the padded raster) = `ksteps` K steps, in at most `cap` slices of whole K steps; slices left empty are dropped
+static void slice_pixels(WgradRoute& p, int units, int ksteps, int split, int cap) {
+    if (split > cap) split = cap;
     if (split < 1) split = 1;
-    if (split > 65535) split = 65535;
     p.per = ((ksteps + split - 1) / split) * kBK;
-    p.split = (M + p.per - 1) / p.per;
-    p.ws_floats = (size_t)p.split * p.tj * p.tn * 4 * 2 * (p.wide ? 2 : 1) * 16 * 64;
+    p.split = (units + p.per - 1) / p.per;
+}
+
+// conv_wgrad_kernel: 128 x bn tiles; takes every geometry (Kw = 256, Co = 64: the stem in its padded layout)
+static WgradRoute plan_wgrad(int M, int Kw, int Co, int split_hint) {
+    WgradRoute p{};
+    p.kernel = LP_CONV_KERNEL_WGRAD;
+    p.bn = Co > 64 ? 128 : 64;
+    p.tiles_a = (Kw + kBM - 1) / kBM;
+    p.tiles_b = p.bn == 128 ? (Co + 127) / 128 : 1;
+    const int tiles = p.tiles_a * p.tiles_b, ksteps = (M + kBK - 1) / kBK;
+    // the chip holds 512 of these workgroups at once (2 per CU, LDS-bound): aim just below a whole number of rounds
+    // (cap: 65535 dates from slices in blockIdx.y; the grid is one-dimensional now, the value is kept so that no split changes)
+    slice_pixels(p, M, ksteps, split_hint > 0 ? split_hint : kWgradWgs / tiles, ksteps < 65535 ? ksteps : 65535);
+    p.ws_floats = (size_t)p.split * tiles * 4 * 2 * (p.bn / 64) * 16 * 64;
+    p.ok = true;
     return p;
 }
 
-// ---- pipelined weight gradient (conv_pipe.h): 256 x BN tiles, one (tile, pixel slice) per workgroup, ~one workgroup per CU
-struct WgradPipePlan {
-    bool ok, swap;
-    int Ka, Cb, tiles_a, tiles_b, bn, split, per;
-    size_t ws_floats;
-};
+// stem_wgrad_nb_kernel (conv_stem_wgrad.h): a K step is 64 consecutive pixels of one output row, byte offsets are 32-bit.  One workgroup
+// (all 256 gradient rows) per pixel slice, ~4 resident per CU (40 KB of LDS each); the workspace holds two 128-row j-tiles per slice
+static WgradRoute plan_stem_wgrad_nb(const ConvGeom& g, int split_hint) {
+    WgradRoute p{};
+    if (g.Wo % 64 != 0 || g.Hi != 2 * g.Ho || g.Wi != 2 * g.Wo || 128ull * g.B * g.Ho * g.Wo >= (1ull << 31) ||
+        8ull * g.B * g.Hi * g.Wi >= (1ull << 31))   // (the kernel forms these byte offsets in signed int)
+        return p;
+    p.kernel = LP_CONV_KERNEL_STEM_WGRAD_NB;
+    p.bn = 64, p.tiles_a = 2, p.tiles_b = 1;
+    const int M = g.B * g.Ho * g.Wo, ksteps = M / kBK;   // (whole rows of 64 pixels: no ragged K step)
+    // 512 - 1024 slices measured equal within 4 %, more are slower: profiles/r05m_stem_wgrad_variants.txt.  (cap: ksteps alone, this
+    // kernel never had the 65535 of conv_wgrad_kernel)
+    slice_pixels(p, M, ksteps, split_hint > 0 ? split_hint : 768, ksteps);
+    p.ws_floats = (size_t)p.split * 2 * 4 * 2 * 16 * 64;
+    p.ok = true;
+    return p;
+}
 
-// `force`: ignore the two performance rules (tile waste, HBM-bound shapes) - LP_WGRAD_PIPE=2, the tests' switch
-static WgradPipePlan plan_wgrad_pipe(const ConvGeom& g, int split_hint, bool force = false) {
-    WgradPipePlan p{};
+// conv_wgrad_pipe_kernel (conv_pipe.h): 256 x bn tiles, one (tile, pixel slice) per workgroup, ~one workgroup per CU
+static WgradRoute plan_wgrad_pipe(const ConvGeom& g, int split_hint) {
+    WgradRoute p{};
     const int M = g.B * g.Ho * g.Wo, Kw = g.R * g.S * g.Ci;
     const bool one = g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && g.Hi == g.Ho && g.Wi == g.Wo;
     if (g.Ci % 8 != 0 || g.Co % 64 != 0 || M < 4 * kBK) return p;
+    p.kernel = LP_CONV_KERNEL_WGRAD_PIPE;
     // a = the 256-wide side.  Ordinary: a = (r, s, ci), b = co.  A 1x1 layer with few input channels is transposed (a = co, b = ci)
     p.swap = one && Kw % 256 != 0 && g.Co % 256 == 0 && Kw % 64 == 0;
     p.Ka = p.swap ? g.Co : Kw;
@@ -1280,11 +1306,11 @@ static WgradPipePlan plan_wgrad_pipe(const ConvGeom& g, int split_hint, bool for
     p.bn = p.Cb % 128 == 0 ? 128 : 64;
     if (p.Cb % p.bn != 0) return p;
     p.tiles_a = (p.Ka + 255) / 256;
-    if (!force && (long long)p.tiles_a * 256 * 8 > (long long)p.Ka * 9) return p;   // a ragged last a-tile may waste an eighth at most (3x3 of 64 channels: 576 -> 768 lost, measured)
-    // HBM-bound shapes (few FLOPs per operand byte: the 1x1 layers of layer1 / layer2) gain nothing from the bigger tile and lose a few
-    // per cent to the 64-B request granularity its LDS swizzle forces on the loads (measured per layer, profiles/archive/r03g_layer_table.txt)
-    if (!force && (long long)p.Ka * p.Cb < 120LL * (p.Ka + p.Cb)) return p;
     p.tiles_b = p.Cb / p.bn;
+    // the two performance rules: a ragged last a-tile may waste an eighth at most (3x3 of 64 channels: 576 -> 768 lost, measured); HBM-bound
+    // shapes (few FLOPs per operand byte: the 1x1 layers of layer1 / layer2) gain nothing from the bigger tile and lose a few per cent to
+    // the 64-B request granularity its LDS swizzle forces on the loads (measured per layer, profiles/archive/r03g_layer_table.txt)
+    p.tuned = (long long)p.tiles_a * 256 * 8 <= (long long)p.Ka * 9 && (long long)p.Ka * p.Cb >= 120LL * (p.Ka + p.Cb);
     const int tiles = p.tiles_a * p.tiles_b;
     const int cus = pipe_max_wgs();
     const int ksteps = (M + kBK - 1) / kBK;
@@ -1299,61 +1325,22 @@ static WgradPipePlan plan_wgrad_pipe(const ConvGeom& g, int split_hint, bool for
             const double cost = rounds * per + 0.04 * (p.bn / 128.0) * s * tiles + 2.0 * rounds;   // (in K steps; 2 per round: ring fill)
             if (cost < best) best = cost, split = s;
         }
-        if (split <= 0) split = 1;
     }
-    if (split > ksteps / 2) split = ksteps / 2;
-    if (split < 1) split = 1;
-    p.per = ((ksteps + split - 1) / split) * kBK;
-    p.split = (M + p.per - 1) / p.per;
+    slice_pixels(p, M, ksteps, split, ksteps / 2);   // (cap: the bound of the cost loop - a slice pays the ring's fill, one K step would be all fill)
     p.ws_floats = (size_t)p.split * tiles * 256 * p.bn;
     p.ok = true;
     return p;
 }
 
-static void launch_wgrad_pipe(const WgradPipePlan& p, const void* x, const void* dy, const ConvGeom& g, float* dw, float* ws, hipStream_t st) {
-    const int M = g.B * g.Ho * g.Wo, Kw = g.R * g.S * g.Ci;
-    const unsigned x_bytes = (unsigned)(2ull * g.B * g.Hi * g.Wi * g.Ci), dy_bytes = (unsigned)(2ull * M * g.Co);
-    WgradPipeGeom wg{};
-    const void *pa = x, *qb = dy;
-    unsigned pa_bytes = x_bytes, qb_bytes = dy_bytes;
-    if (p.swap) {   // a = co (rows of dy), b = ci (rows of x): both plain
-        wg = WgradPipeGeom{g.B, g.Ho, g.Wo, g.Ho, g.Wo, g.Co, 1, 1, 1, 0, p.Ka, p.Cb, 1};
-        pa = dy, qb = x, pa_bytes = dy_bytes, qb_bytes = x_bytes;
-    } else {
-        const int plain = g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && g.Hi == g.Ho && g.Wi == g.Wo;
-        wg = WgradPipeGeom{g.B, g.Hi, g.Wi, g.Ho, g.Wo, g.Ci, g.R, g.S, g.stride, g.pad, p.Ka, p.Cb, plain};
-    }
-    const int tiles = p.tiles_a * p.tiles_b;
-    const FastDiv dhw = make_fastdiv(g.Ho * g.Wo), dwo = make_fastdiv(g.Wo);
-    g_last_conv_kernel = LP_CONV_KERNEL_WGRAD_PIPE;
-    const int sa = p.swap ? Kw : 1, sb = p.swap ? 1 : Kw;   // dW[co][kw]: ordinary a = kw index, b = co; swapped a = co, b = kw index
-    if (p.bn == 128) {
-        hipLaunchKernelGGL((conv_wgrad_pipe_kernel<128>), dim3(tiles * p.split), dim3(512), 0, st, (const unsigned short*)pa,
-                           (const unsigned short*)qb, pa_bytes, qb_bytes, wg, M, tiles, p.tiles_b, p.per, dhw, dwo, ws);
-        hipLaunchKernelGGL((wgrad_pipe_reduce_kernel<128>), dim3(tiles * 256 * 128 / 64), dim3(256), 0, st, ws, p.split, tiles, p.tiles_b, p.Ka,
-                           p.Cb, sa, sb, dw);
-    } else {
-        hipLaunchKernelGGL((conv_wgrad_pipe_kernel<64>), dim3(tiles * p.split), dim3(512), 0, st, (const unsigned short*)pa,
-                           (const unsigned short*)qb, pa_bytes, qb_bytes, wg, M, tiles, p.tiles_b, p.per, dhw, dwo, ws);
-        hipLaunchKernelGGL((wgrad_pipe_reduce_kernel<64>), dim3(tiles * 256 * 64 / 64), dim3(256), 0, st, ws, p.split, tiles, p.tiles_b, p.Ka,
-                           p.Cb, sa, sb, dw);
-    }
-}
-
-// ---- 3x3 / stride 1 / pad 1 weight gradient from a staged neighbourhood (conv_wgrad_nb.h): one workgroup per (64 ci, bn co, slice of the
+// conv_wgrad_nb_kernel (conv_wgrad_nb.h): 3x3 / stride 1 / pad 1 from a staged neighbourhood, one workgroup per (64 ci, bn co, slice of the
 // padded raster), ONE resident round (a workgroup's partial tile is 9 x 64 x bn fp32: more slices than CUs only add workspace traffic)
-struct WgradNbPlan {
-    bool ok;
-    int bn, kh, tiles_a, tiles_b, split, per, PT, lead;
-    size_t ws_floats;
-};
-
-static WgradNbPlan plan_wgrad_nb(const ConvGeom& g, int split_hint) {
-    WgradNbPlan p{};
+static WgradRoute plan_wgrad_nb(const ConvGeom& g, int split_hint) {
+    WgradRoute p{};
     if (g.R != 3 || g.S != 3 || g.stride != 1 || g.pad != 1 || g.Hi != g.Ho || g.Wi != g.Wo || g.Ci % 64 != 0 || g.Co % 64 != 0) return p;
     if (g.Wi > 126) return p;   // the x window holds 2 lead + 3 chunks of 64 raster rows, lead = 1 + (W + 1) / 64 <= 2
     const long long pt = (long long)g.B * (g.Hi + 1) * (g.Wi + 1);
     if (pt + 64 * 8 >= (1LL << 31)) return p;
+    p.kernel = LP_CONV_KERNEL_WGRAD_NB;
     p.PT = (int)pt;
     p.lead = 1 + (g.Wi + 1) / 64;
     p.bn = g.Co % 128 == 0 ? 128 : 64;
@@ -1374,33 +1361,97 @@ static WgradNbPlan plan_wgrad_nb(const ConvGeom& g, int split_hint) {
             const double cost = rounds * (per * step_us + 15.0) + 0.06 * s * tiles;
             if (cost < best) best = cost, split = s;
         }
-        if (split <= 0) split = 1;
     }
-    if (split > ksteps) split = ksteps;
-    if (split < 1) split = 1;
-    if (split > 65535) split = 65535;
-    p.per = ((ksteps + split - 1) / split) * kBK;
-    p.split = (p.PT + p.per - 1) / p.per;
+    slice_pixels(p, p.PT, ksteps, split, ksteps < 65535 ? ksteps : 65535);   // (cap: as conv_wgrad_kernel's)
     p.ws_floats = (size_t)p.split * p.kh * tiles * 9 * 64 * p.bn;
     p.ok = true;
     return p;
 }
 
-static void launch_wgrad_nb(const WgradNbPlan& p, const void* x, const void* dy, const ConvGeom& g, float* dw, float* ws, hipStream_t st) {
+// the 7x7 / 2 stem on NHWC4 input (lp_stem_wgrad's geometry; lp_conv_wgrad_workspace_bytes recognises it by the same test)
+static bool is_stem(const ConvGeom& g) { return g.R == 7 && g.S == 7 && g.stride == 2 && g.pad == 3 && g.Ci == 4 && g.Co == 64; }
+
+struct WgradCandidates {
+    int n;
+    WgradRoute r[3];
+};
+
+// The plans this geometry admits, best first; conv_wgrad_kernel closes every list.  Shape rules live in the plans above and here only.
+static WgradCandidates wgrad_candidates(const ConvGeom& g, bool stem, int split_hint) {
+    WgradCandidates c{};
+    const int M = g.B * g.Ho * g.Wo;
+    auto add = [&c](const WgradRoute& p) {
+        if (p.ok) c.r[c.n++] = p;
+    };
+    if (stem) {
+        // (LP_STEM_WGRAD_NB=0 withdraws the candidate instead of losing in route_wgrad: the stem's workspace size has followed that switch
+        // since the kernel came, and the size returned stays what it was)
+        if (lp_switches().stem_wgrad_nb != 0) add(plan_stem_wgrad_nb(g, split_hint));
+        add(plan_wgrad(M, 256, 64, split_hint));
+    } else {
+        add(plan_wgrad_nb(g, split_hint));
+        add(plan_wgrad_pipe(g, split_hint));
+        add(plan_wgrad(M, g.R * g.S * g.Ci, g.Co, split_hint));
+    }
+    return c;
+}
+
+// The first candidate the switches let run.  Switch rules live here only: LP_CONV_PIPE=0 and a bias gradient (only conv_wgrad_kernel forms
+// one) leave conv_wgrad_kernel; LP_WGRAD_PIPE is the A/B switch (0: conv_wgrad_kernel, 2: conv_wgrad_pipe_kernel wherever it can run), and
+// LP_WGRAD_NB acts under LP_WGRAD_PIPE=1 only, so that the two A/B arms keep their meaning
+static const WgradRoute& route_wgrad(const WgradCandidates& c, const LpSwitches& sw, bool dbias) {
+    const bool pipe = !dbias && sw.conv_pipe != 0;
+    for (int i = 0; i < c.n - 1; ++i) {
+        const WgradRoute& r = c.r[i];
+        if (r.kernel == LP_CONV_KERNEL_WGRAD_NB && !(pipe && sw.wgrad_pipe == 1 && sw.wgrad_nb != 0)) continue;
+        if (r.kernel == LP_CONV_KERNEL_WGRAD_PIPE && !(pipe && sw.wgrad_pipe != 0 && (sw.wgrad_pipe == 2 || r.tuned))) continue;
+        return r;
+    }
+    return c.r[c.n - 1];
+}
+
+template <int BN>
+static void launch_wgrad(const WgradRoute& p, const void* x, const void* dy, const ConvGeom& g, float* dw, float* dbias, float* ws, hipStream_t st) {
+    const int M = g.B * g.Ho * g.Wo, Kw = g.R * g.S * g.Ci, tiles = p.tiles_a * p.tiles_b;
+    const unsigned x_bytes = (unsigned)(2ull * g.B * g.Hi * g.Wi * g.Ci), dy_bytes = (unsigned)(2ull * M * g.Co);
+    TnExt ext{};
+    ext.col_sums = dbias;
+    const auto kernel = dbias ? conv_wgrad_kernel<BN, false, true> : conv_wgrad_kernel<BN, false, false>;
+    hipLaunchKernelGGL(kernel, dim3(tiles * p.split), dim3(256), 0, st, (const unsigned short*)x, (const unsigned short*)dy, x_bytes, dy_bytes, g,
+                       M, Kw, tiles, p.tiles_b, p.per, make_fastdiv(g.Ho * g.Wo), make_fastdiv(g.Wo), ws, ext);
+    launch_wgrad_reduce<BN>(ws, p.split, tiles, p.tiles_b, Kw, g.Co, dw, st);
+}
+
+template <int BN>
+static void launch_wgrad_pipe(const WgradRoute& p, const void* x, const void* dy, const ConvGeom& g, float* dw, float* ws, hipStream_t st) {
+    const int M = g.B * g.Ho * g.Wo, Kw = g.R * g.S * g.Ci;
+    const unsigned x_bytes = (unsigned)(2ull * g.B * g.Hi * g.Wi * g.Ci), dy_bytes = (unsigned)(2ull * M * g.Co);
+    WgradPipeGeom wg{};
+    const void *pa = x, *qb = dy;
+    unsigned pa_bytes = x_bytes, qb_bytes = dy_bytes;
+    if (p.swap) {   // a = co (rows of dy), b = ci (rows of x): both plain
+        wg = WgradPipeGeom{g.B, g.Ho, g.Wo, g.Ho, g.Wo, g.Co, 1, 1, 1, 0, p.Ka, p.Cb, 1};
+        pa = dy, qb = x, pa_bytes = dy_bytes, qb_bytes = x_bytes;
+    } else {
+        const int plain = g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && g.Hi == g.Ho && g.Wi == g.Wo;
+        wg = WgradPipeGeom{g.B, g.Hi, g.Wi, g.Ho, g.Wo, g.Ci, g.R, g.S, g.stride, g.pad, p.Ka, p.Cb, plain};
+    }
+    const int tiles = p.tiles_a * p.tiles_b;
+    const int sa = p.swap ? Kw : 1, sb = p.swap ? 1 : Kw;   // dW[co][kw]: ordinary a = kw index, b = co; swapped a = co, b = kw index
+    hipLaunchKernelGGL((conv_wgrad_pipe_kernel<BN>), dim3(tiles * p.split), dim3(512), 0, st, (const unsigned short*)pa, (const unsigned short*)qb,
+                       pa_bytes, qb_bytes, wg, M, tiles, p.tiles_b, p.per, make_fastdiv(g.Ho * g.Wo), make_fastdiv(g.Wo), ws);
+    hipLaunchKernelGGL((wgrad_pipe_reduce_kernel<BN>), dim3(tiles * 256 * BN / 64), dim3(256), 0, st, ws, p.split, tiles, p.tiles_b, p.Ka, p.Cb,
+                       sa, sb, dw);
+}
+
+template <int BN>
+static void launch_wgrad_nb(const WgradRoute& p, const void* x, const void* dy, const ConvGeom& g, float* dw, float* ws, hipStream_t st) {
     const unsigned x_bytes = (unsigned)(2ull * g.B * g.Hi * g.Wi * g.Ci), dy_bytes = (unsigned)(2ull * g.B * g.Ho * g.Wo * g.Co);
     const WgradNbGeom ng{g.B, g.Hi, g.Wi, g.Ci, g.Co, p.PT, p.lead};
     const int tiles = p.tiles_a * p.tiles_b;
-    const FastDiv dwp = make_fastdiv(g.Wi + 1), dhp = make_fastdiv(g.Hi + 1);
-    g_last_conv_kernel = LP_CONV_KERNEL_WGRAD_NB;
-    if (p.bn == 128) {
-        hipLaunchKernelGGL((conv_wgrad_nb_kernel<128>), dim3(tiles * p.split), dim3(512), 0, st, (const unsigned short*)x, (const unsigned short*)dy,
-                           x_bytes, dy_bytes, ng, tiles, p.tiles_b, p.per, dwp, dhp, ws);
-        hipLaunchKernelGGL((wgrad_nb_reduce_kernel<128>), dim3(tiles * 9 * 128), dim3(256), 0, st, ws, p.split * p.kh, tiles, p.tiles_b, g.Ci, dw);
-    } else {
-        hipLaunchKernelGGL((conv_wgrad_nb_kernel<64>), dim3(tiles * p.split), dim3(512), 0, st, (const unsigned short*)x, (const unsigned short*)dy,
-                           x_bytes, dy_bytes, ng, tiles, p.tiles_b, p.per, dwp, dhp, ws);
-        hipLaunchKernelGGL((wgrad_nb_reduce_kernel<64>), dim3(tiles * 9 * 64), dim3(256), 0, st, ws, p.split * p.kh, tiles, p.tiles_b, g.Ci, dw);
-    }
+    hipLaunchKernelGGL((conv_wgrad_nb_kernel<BN>), dim3(tiles * p.split), dim3(512), 0, st, (const unsigned short*)x, (const unsigned short*)dy,
+                       x_bytes, dy_bytes, ng, tiles, p.tiles_b, p.per, make_fastdiv(g.Wi + 1), make_fastdiv(g.Hi + 1), ws);
+    hipLaunchKernelGGL((wgrad_nb_reduce_kernel<BN>), dim3(tiles * 9 * BN), dim3(256), 0, st, ws, p.split * p.kh, tiles, p.tiles_b, g.Ci, dw);
 }
 
 static bool geom_ok(const lp_conv_geom* c) {
@@ -1711,42 +1762,15 @@ extern "C" int lp_conv_dgrad_bn(const void* dy, const void* wd, const lp_conv_ge
     return conv_dgrad_impl(dy, wd, geom, nullptr, addend, relu_mask, dx_bf16, nullptr, geom->Ci, 0, 0, bn, stream);
 }
 
-// stem_wgrad_nb_kernel (conv_stem_wgrad.h): a K step is 64 consecutive pixels of one output row, byte offsets are 32-bit
-static bool stem_wgrad_nb_ok(const lp::ConvGeom& g) {
-    return lp::lp_switches().stem_wgrad_nb != 0 && g.Wo % 64 == 0 && g.Hi == 2 * g.Ho && g.Wi == 2 * g.Wo &&
-           128ull * g.B * g.Ho * g.Wo < (1ull << 31) && 8ull * g.B * g.Hi * g.Wi < (1ull << 31);   // (the kernel forms these byte offsets in signed int)
-}
-// one workgroup (all 256 gradient rows) per pixel slice, ~4 resident per CU (40 KB of LDS each); the workspace holds two 128-row j-tiles per slice
-static lp::WgradPlan plan_stem_wgrad_nb(int M, int split_hint) {
-    lp::WgradPlan p{};
-    const int ksteps = M / lp::kBK;
-    int split = split_hint > 0 ? split_hint : 768;   // (512 - 1024 slices measured equal within 4 %, more are slower: profiles/r05m_stem_wgrad_variants.txt)
-    if (split > ksteps) split = ksteps;
-    if (split < 1) split = 1;
-    p.per = ((ksteps + split - 1) / split) * lp::kBK;
-    p.split = (M + p.per - 1) / p.per;
-    p.tj = 2, p.tn = 1, p.wide = false;
-    p.ws_floats = (size_t)p.split * 2 * 4 * 2 * 16 * 64;
-    return p;
-}
-
+// room for every candidate of the geometry: the size suffices whichever kernel the switches route the launch to
 extern "C" size_t lp_conv_wgrad_workspace_bytes(const lp_conv_geom* geom, int split_hint) {
     using namespace lp;
     if (!geom_ok(geom)) return 0;
-    ConvGeom g = to_geom(geom);
-    const bool stem = (g.Ci == 4 && g.R == 7);
-    const int Kw = stem ? 256 : g.R * g.S * g.Ci;
-    size_t fl = plan_wgrad(g.B * g.Ho * g.Wo, Kw, g.Co, split_hint, kWgradWgs).ws_floats;
-    if (stem && stem_wgrad_nb_ok(g)) {
-        const size_t nb = plan_stem_wgrad_nb(g.B * g.Ho * g.Wo, split_hint).ws_floats;
-        if (nb > fl) fl = nb;
-    }
-    if (!stem) {   // either kernel may take the launch (LP_CONV_PIPE): room for both plans
-        const WgradPipePlan pp = plan_wgrad_pipe(g, split_hint, true);   // (the forced plan is the larger one)
-        if (pp.ok && pp.ws_floats > fl) fl = pp.ws_floats;
-        const WgradNbPlan np = plan_wgrad_nb(g, split_hint);
-        if (np.ok && np.ws_floats > fl) fl = np.ws_floats;
-    }
+    const ConvGeom g = to_geom(geom);
+    const WgradCandidates c = wgrad_candidates(g, is_stem(g), split_hint);
+    size_t fl = 0;
+    for (int i = 0; i < c.n; ++i)
+        if (c.r[i].ws_floats > fl) fl = c.r[i].ws_floats;
     return fl * sizeof(float);
 }
 
@@ -1759,47 +1783,22 @@ static int conv_wgrad_impl(const void* x, const void* dy, const lp_conv_geom* ge
     if (g.Ci % 8 != 0 || g.Co % 8 != 0 || (long long)g.B * g.Hi * g.Wi * g.Ci >= (1LL << 31) ||
         (long long)g.B * g.Ho * g.Wo * g.Co >= (1LL << 31))
         return LP_ERR_UNSUPPORTED;
-    const int M = g.B * g.Ho * g.Wo, Kw = g.R * g.S * g.Ci;
-    const unsigned x_bytes = (unsigned)(2ull * g.B * g.Hi * g.Wi * g.Ci), dy_bytes = (unsigned)(2ull * M * g.Co);
-    const WgradPlan p = plan_wgrad(M, Kw, g.Co, split_hint, kWgradWgs);
+    const WgradCandidates c = wgrad_candidates(g, false, split_hint);
+    const WgradRoute& p = route_wgrad(c, lp_switches(), dbias != nullptr);
     LP_REQUIRE(workspace_bytes >= p.ws_floats * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    const int wpe = lp_switches().wgrad_pipe;   // (LP_WGRAD_PIPE, A/B: 0 keeps the weight gradients on conv_wgrad_kernel; 2 = wherever it can run)
-    if (!dbias && conv_pipe_enabled() && wpe == 1 && lp_switches().wgrad_nb != 0) {   // (LP_WGRAD_PIPE=0 / 2 keep their meaning: the A/B arms)
-        const WgradNbPlan np = plan_wgrad_nb(g, split_hint);
-        if (np.ok && workspace_bytes >= np.ws_floats * sizeof(float)) {
-            launch_wgrad_nb(np, x, dy, g, dw, ws, st);
-            return launch_status();
-        }
-    }
-    if (!dbias && conv_pipe_enabled() && wpe != 0) {
-        const WgradPipePlan pp = plan_wgrad_pipe(g, split_hint, wpe == 2);
-        if (pp.ok && workspace_bytes >= pp.ws_floats * sizeof(float)) {
-            launch_wgrad_pipe(pp, x, dy, g, dw, ws, st);
-            return launch_status();
-        }
-    }
-    g_last_conv_kernel = LP_CONV_KERNEL_WGRAD;
-    const int tiles = p.tj * p.tn;
-    TnExt ext{};
-    ext.col_sums = dbias;
-    const dim3 grid(tiles * p.split), block(256);
-    const FastDiv dhw = make_fastdiv(g.Ho * g.Wo), dwo = make_fastdiv(g.Wo);
-    const unsigned short *xs = (const unsigned short*)x, *dys = (const unsigned short*)dy;
-#define LP_WGRAD_LAUNCH(BN_, CS_)                                                                                                \
-    hipLaunchKernelGGL((conv_wgrad_kernel<BN_, false, CS_>), grid, block, 0, st, xs, dys, x_bytes, dy_bytes, g, M, Kw, tiles, p.tn, \
-                       p.per, dhw, dwo, ws, ext)
-    if (p.wide) {
-        if (dbias) LP_WGRAD_LAUNCH(128, true);
-        else LP_WGRAD_LAUNCH(128, false);
-        launch_wgrad_reduce<128>(ws, p.split, tiles, p.tn, Kw, g.Co, dw, st);
+    g_last_conv_kernel = p.kernel;
+    if (p.kernel == LP_CONV_KERNEL_WGRAD_NB) {
+        if (p.bn == 128) launch_wgrad_nb<128>(p, x, dy, g, dw, ws, st);
+        else launch_wgrad_nb<64>(p, x, dy, g, dw, ws, st);
+    } else if (p.kernel == LP_CONV_KERNEL_WGRAD_PIPE) {
+        if (p.bn == 128) launch_wgrad_pipe<128>(p, x, dy, g, dw, ws, st);
+        else launch_wgrad_pipe<64>(p, x, dy, g, dw, ws, st);
     } else {
-        if (dbias) LP_WGRAD_LAUNCH(64, true);
-        else LP_WGRAD_LAUNCH(64, false);
-        launch_wgrad_reduce<64>(ws, p.split, tiles, p.tn, Kw, g.Co, dw, st);
+        if (p.bn == 128) launch_wgrad<128>(p, x, dy, g, dw, dbias, ws, st);
+        else launch_wgrad<64>(p, x, dy, g, dw, dbias, ws, st);
     }
-#undef LP_WGRAD_LAUNCH
     return launch_status();
 }
 
@@ -1898,24 +1897,22 @@ extern "C" int lp_stem_wgrad(const void* x4, const void* dy, const lp_conv_geom*
     using namespace lp;
     LP_REQUIRE(x4 && dy && geom_ok(geom) && dw && workspace);
     ConvGeom g = to_geom(geom);
-    if (g.R != 7 || g.S != 7 || g.stride != 2 || g.pad != 3 || g.Ci != 4 || g.Co != 64) return LP_ERR_UNSUPPORTED;
+    if (!is_stem(g)) return LP_ERR_UNSUPPORTED;
+    const WgradCandidates c = wgrad_candidates(g, true, split_hint);
+    const WgradRoute& p = route_wgrad(c, lp_switches(), false);
+    LP_REQUIRE(workspace_bytes >= p.ws_floats * sizeof(float));
     const int M = g.B * g.Ho * g.Wo, Kw = 256;
+    const unsigned short *xs = (const unsigned short*)x4, *dys = (const unsigned short*)dy;
+    const FastDiv dhw = make_fastdiv(g.Ho * g.Wo), dwo = make_fastdiv(g.Wo);
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    if (stem_wgrad_nb_ok(g)) {   // one workgroup per pixel slice forms all 256 gradient rows from the staged input neighbourhood
-        const WgradPlan p = plan_stem_wgrad_nb(M, split_hint);
-        LP_REQUIRE(workspace_bytes >= p.ws_floats * sizeof(float));
-        g_last_conv_kernel = LP_CONV_KERNEL_STEM_WGRAD_NB;
-        hipLaunchKernelGGL(stem_wgrad_nb_kernel, dim3(p.split), dim3(256), 0, st, (const unsigned short*)x4, (const unsigned short*)dy,
-                           (unsigned)(8ull * g.B * g.Hi * g.Wi), (unsigned)(128ull * M), g, M, p.per, make_fastdiv(g.Ho * g.Wo), make_fastdiv(g.Wo), ws);
-        launch_wgrad_reduce<64>(ws, p.split, 2, 1, Kw, 64, dw, st);
-        return launch_status();
-    }
-    const WgradPlan p = plan_wgrad(M, Kw, 64, split_hint, kWgradWgs);
-    LP_REQUIRE(workspace_bytes >= p.ws_floats * sizeof(float));
-    g_last_conv_kernel = LP_CONV_KERNEL_WGRAD;
-    hipLaunchKernelGGL((conv_wgrad_kernel<64, true>), dim3(p.tj * p.split), dim3(256), 0, st, (const unsigned short*)x4,
-                       (const unsigned short*)dy, 0u, 0u, g, M, Kw, p.tj, 1, p.per, make_fastdiv(g.Ho * g.Wo), make_fastdiv(g.Wo), ws, TnExt{});
-    launch_wgrad_reduce<64>(ws, p.split, p.tj, 1, Kw, 64, dw, st);
+    g_last_conv_kernel = p.kernel;
+    if (p.kernel == LP_CONV_KERNEL_STEM_WGRAD_NB)   // one workgroup per pixel slice forms all 256 gradient rows from the staged input neighbourhood
+        hipLaunchKernelGGL(stem_wgrad_nb_kernel, dim3(p.split), dim3(256), 0, st, xs, dys, (unsigned)(8ull * g.B * g.Hi * g.Wi),
+                           (unsigned)(128ull * M), g, M, p.per, dhw, dwo, ws);
+    else
+        hipLaunchKernelGGL((conv_wgrad_kernel<64, true>), dim3(p.tiles_a * p.split), dim3(256), 0, st, xs, dys, 0u, 0u, g, M, Kw, p.tiles_a, 1,
+                           p.per, dhw, dwo, ws, TnExt{});
+    launch_wgrad_reduce<64>(ws, p.split, p.tiles_a, 1, Kw, 64, dw, st);
     return launch_status();
 }

@@ -3,16 +3,19 @@ nine filter taps - a circular window of the input in a padded raster with shared
 Against torch's weight gradient of the same bf16-rounded operands and against conv_wgrad_kernel, on the emulator and (-m gpu) on the
 device through the same C ABI call.  Shapes are the smallest at which the kernel can still go wrong."""
 
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from lightning_pose_amd import _lib
 from tests.hipemu import emu
 
 pytestmark = pytest.mark.usefixtures("kernel_backend")
 
-KERNEL_WGRAD, KERNEL_WGRAD_PIPE, KERNEL_WGRAD_NB = 2, 3, 9   # include/lp_hip.h: LP_CONV_KERNEL_*
+KERNEL_WGRAD, KERNEL_WGRAD_PIPE, KERNEL_WGRAD_NB = _lib.CONV_KERNEL_WGRAD, _lib.CONV_KERNEL_WGRAD_PIPE, _lib.CONV_KERNEL_WGRAD_NB
 
 CASES = [
     # B, H, W, Ci, Co
@@ -94,3 +97,34 @@ def test_other_shapes_are_not_routed_to_it(B, H, W, Ci, Co, R, stride, pad):
     dw = emu.conv_wgrad(xb, dyb, g)
     assert emu.lib().lp_conv_last_kernel() in (KERNEL_WGRAD, KERNEL_WGRAD_PIPE)
     assert np.isfinite(dw).all() and np.abs(dw).max() > 0
+
+
+@pytest.mark.parametrize("switch", [None, ("LP_WGRAD_NB", "0"), ("LP_WGRAD_PIPE", "0"), ("LP_WGRAD_PIPE", "2")])
+@pytest.mark.parametrize("stem", [False, True])
+def test_the_routed_plans_workspace_is_required(stem, switch, monkeypatch):
+    """A workspace smaller than the plan of the kernel the launch is routed to is LP_ERR_ARGUMENT before anything is launched - never a
+    quiet move to a slower kernel: dw and lp_conv_last_kernel() stay as they were.  256 bytes are below every kernel's smallest plan (one
+    slice of one 64-wide tile is 32 KB); exactly lp_conv_wgrad_workspace_bytes() succeeds under every switch setting."""
+    if switch:
+        monkeypatch.setenv(*switch)
+    g = emu.geom(1, 128, 128, 4, 64, 7, 7, 2, 3) if stem else emu.geom(1, 16, 16, 64, 64, 3, 3, 1, 1)
+    call = emu.lib().lp_stem_wgrad if stem else emu.lib().lp_conv_wgrad
+    gen = torch.Generator().manual_seed(5)
+    xb = emu.Buf(emu.to_bf16_bits(torch.randn(g.B, g.Hi, g.Wi, g.Ci, generator=gen)))
+    db = emu.Buf(emu.to_bf16_bits(torch.randn(g.B, g.Ho, g.Wo, g.Co, generator=gen)))
+    nws = emu.lib().lp_conv_wgrad_workspace_bytes(C.byref(g), 0)
+    assert nws > 256
+    ws = emu.Z(nws, np.uint8)
+    # a forward call first: its kernel id (conv_igemm_kernel / conv_pipe_kernel) is none of the weight-gradient ids
+    emu.conv_fwd(emu.to_bf16_bits(torch.randn(1, 4, 4, 64, generator=gen)), emu.to_bf16_bits(torch.randn(64, 64, generator=gen)),
+                 emu.geom(1, 4, 4, 64, 64, 1, 1, 1, 0))
+    before = emu.lib().lp_conv_last_kernel()
+    assert before in (_lib.CONV_KERNEL_IGEMM, _lib.CONV_KERNEL_PIPE)
+    sentinel = np.full((64, 256) if stem else (g.Co, 9 * g.Ci), -7.5, np.float32)
+    dw = emu.Buf(sentinel)
+    assert call(xb.p, db.p, C.byref(g), dw.p, 0, ws.p, 256, emu.stream()) == -1   # LP_ERR_ARGUMENT
+    assert np.array_equal(dw.np(), sentinel)
+    assert emu.lib().lp_conv_last_kernel() == before
+    emu.ok(call(xb.p, db.p, C.byref(g), dw.p, 0, ws.p, nws, emu.stream()))
+    assert emu.lib().lp_conv_last_kernel() not in (_lib.CONV_KERNEL_IGEMM, _lib.CONV_KERNEL_PIPE)
+    assert np.isfinite(dw.np()).all() and not np.array_equal(dw.np(), sentinel)
