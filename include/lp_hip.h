@@ -50,8 +50,8 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * not only when symbols come or go.  lp_version() returns the value the library was built with; a caller compares the two before its first
  * call (lightning_pose_amd/_lib.py raises LpHipUnavailable on a mismatch) - a library built against an older header would otherwise take,
  * e.g., the stream argument for an inserted flag without any error.  History: 131 = round 5 (decode `prune`, bn_bwd `terms_ws`), 140 = round 6,
- * 144 = the multi-view token assembly (lp_vit_mv_tokens_*). */
-#define LP_HIP_ABI_VERSION 144
+ * 144 = the multi-view token assembly (lp_vit_mv_tokens_*), 145 = the camera geometry of the calibrated 3-D losses (lp_cam_*). */
+#define LP_HIP_ABI_VERSION 145
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -526,6 +526,37 @@ int lp_vit_mv_tokens_fwd(const void* patch_bf16, const float* pos, const float* 
 size_t lp_vit_mv_tokens_bwd_workspace_bytes(int B, int V, int Np, int D);
 int lp_vit_mv_tokens_bwd(const float* dx, int B, int V, int Np, int D, void* dpatch_bf16, float* dpos, float* dview, void* workspace,
                          size_t workspace_bytes, lp_stream_t stream);
+/* ---- camera geometry of the calibrated multi-view losses (csrc/cameras.hip; reference data/cameras.py, data/bboxes.py:194-219,
+ * losses/losses.py:999-1126).  All fp32.  points (B, V, K, 2) frame px; intrinsics (B, V, 3, 3); extrinsics (B, V, 3, 4); dist12 (B, V, 12):
+ * OpenCV order k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4, shorter sets padded with zeros by the caller; bbox (B, 4 V) [x, y, h, w] per view or
+ * NULL.  P = V (V - 1) / 2 camera pairs in itertools.combinations order.  V <= LP_CAM_MAX_VIEWS (LP_ERR_UNSUPPORTED otherwise).
+ *   undistort   x0 = (u - cx) / fx, y0 = (v - cy) / fy; 5 fixed-point iterations of x = (x0 - dx(x, y)) * inv(x, y)
+ *   triangulate h = right singular vector of the smallest singular value of the 4 x 4 DLT matrix; X = h[:3] / h[3] (|h[3]| > 1e-8, else h[:3]);
+ *               a keypoint that is NaN in either view gives NaN for that (pair, keypoint) and takes no gradient
+ *   project     Xc = R X + t; (x, y) = Xc[:2] / Xc[2] (same guard); the distortion model forward; u = fx x + cx, v = fy y + cy;
+ *               with bbox: u = (u - bx) / bw * model_w, v = (v - by) / bh * model_h
+ * lp_cam_chain_fwd: p3d (B, P, K, 3) = every pair's triangulation; p2d (B, V, K, 2) (may be NULL: triangulation only) = the mean of the pairs
+ * (one NaN pair makes it NaN) projected into every view.  ONE launch, one workgroup per sample.
+ * lp_cam_chain_bwd: gpoints (B, V, K, 2) = d / d points of (g3d . p3d + g2d . p2d); g3d or g2d may be NULL (not both); p3d (the forward's
+ * output) is required with g2d.  Written, not accumulated; 0 for a NaN point; a NaN mean passes no gradient from g2d.  ONE launch; sums in a
+ * fixed order, no atomics: the same input gives the same bits.  workspace: lp_cam_chain_workspace_bytes(B, V, K) bytes (0 for an
+ * unsupported shape), contents undefined before and after. */
+#define LP_CAM_MAX_VIEWS 32
+size_t lp_cam_chain_workspace_bytes(int B, int V, int K);
+int lp_cam_chain_fwd(const float* points, const float* intrinsics, const float* extrinsics, const float* dist12, const float* bbox, float model_h,
+                     float model_w, int B, int V, int K, float* p3d, float* p2d, lp_stream_t stream);
+int lp_cam_chain_bwd(const float* points, const float* intrinsics, const float* extrinsics, const float* dist12, const float* bbox, float model_h,
+                     float model_w, int B, int V, int K, const float* p3d, const float* g3d, const float* g2d, void* workspace,
+                     size_t workspace_bytes, float* gpoints, lp_stream_t stream);
+/* stand-alone projection of points_3d (B, K, 3) into every view -> p2d (B, V, K, 2), and its backward g3d (B, K, 3) = sum over the views (in
+ * order) of the projection's transpose applied to g2d; 0 for a NaN point */
+int lp_cam_project_fwd(const float* points_3d, const float* intrinsics, const float* extrinsics, const float* dist12, const float* bbox,
+                       float model_h, float model_w, int B, int V, int K, float* p2d, lp_stream_t stream);
+int lp_cam_project_bwd(const float* points_3d, const float* intrinsics, const float* extrinsics, const float* dist12, const float* bbox,
+                       float model_h, float model_w, int B, int V, int K, const float* g2d, float* g3d, lp_stream_t stream);
+/* loss = mean over the valid (b, p, k) of ||targ_3d[b, k] - pred_3d[b, p, k]||_2 (invalid: a NaN in either; 0 if none is valid);
+ * grad_unit (B, P, K, 3) = d loss / d pred_3d for upstream 1 (0 where invalid or where the distance is exactly 0).  One launch. */
+int lp_cam_pairwise_fwd_bwd(const float* targ_3d, const float* pred_3d, int B, int P, int K, float* loss, float* grad_unit, lp_stream_t stream);
 /* y (R,D) (+)= w (R,Q) @ x (Q,D), or with transpose_w: y (Q,D) (+)= w^T @ x (R,D): bicubic position-embedding interpolation */
 int lp_small_matmul(const float* w, const float* x, int R, int Q, int D, int transpose_w, int accumulate, float* y, lp_stream_t stream);
 /* x_out = x (+ delta_bf16);  y = LayerNorm(x_out) in bf16;  drop_T > 0: rows with row % drop_T == 0 ([CLS]) are dropped from y and

@@ -63,7 +63,7 @@ AUG_LOCAL_BLUR_COARSE, AUG_LOCAL_EMBOSS = 0, 1
 AUG_ELASTIC_MAX_RADIUS = 20
 TF_NONE, TF_SINGLE, TF_PER_FRAME, TF_PER_VIEW = 0, 1, 2, 3
 
-ABI_VERSION = 144   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
+ABI_VERSION = 145   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -146,6 +146,12 @@ PROTOTYPES = {
     "lp_vit_mv_tokens_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "lp_vit_mv_tokens_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "lp_vit_mv_tokens_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "lp_cam_chain_workspace_bytes": (_Z, [_I, _I, _I]),
+    "lp_cam_chain_fwd": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _P, _P, _P]),
+    "lp_cam_chain_bwd": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _P, _P, _P, _P, _Z, _P, _P]),
+    "lp_cam_project_fwd": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _P, _P]),
+    "lp_cam_project_bwd": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _P, _P, _P]),
+    "lp_cam_pairwise_fwd_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "lp_small_matmul": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "lp_layernorm_fwd": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P]),
     "lp_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),

@@ -1,4 +1,5 @@
-"""``model_to_frame_batch`` (reference: lightning_pose/data/bboxes.py:222-288, norm_to_frame :74-105)."""
+"""``model_to_frame_batch`` and ``frame_to_model_batch`` (reference: lightning_pose/data/bboxes.py:194-288, frame_to_norm :45-71,
+norm_to_frame :74-105, norm_to_model :129-147)."""
 
 from __future__ import annotations
 
@@ -38,3 +39,17 @@ def model_to_frame_batch(batch_dict: dict, model_keypoints: torch.Tensor, in_pla
         bbox = bbox[2:-2]
     fm = ops.DecodeFrameMap(None, False, bbox, views, mh, mw, k)
     return ops.frame_map_apply(model_keypoints, fm)
+
+
+def frame_to_model_batch(batch_dict: dict, frame_keypoints: torch.Tensor) -> torch.Tensor:
+    """(batch, num_views, num_keypoints, 2) keypoints in original-frame px -> network-input px: per view, ``(kp - bbox[x, y]) / bbox[w, h] *
+    model[w, h]`` with ``batch_dict['bbox'][:, 4 v : 4 v + 4]`` = [x, y, h, w] (reference :194-219).  A few elementwise torch operations on
+    whatever device the keypoints live on (differentiable); the training step does not come through here - its reprojection applies this map
+    inside the fused geometry kernel (``ops.camera_chain``)."""
+    batch, views, _, _ = frame_keypoints.shape
+    mh, mw = model_dims(batch_dict)
+    bbox = batch_dict["bbox"].to(device=frame_keypoints.device, dtype=frame_keypoints.dtype).reshape(batch, views, 4)
+    offset = bbox[:, :, None, 0:2]                                  # x, y
+    size = torch.stack([bbox[:, :, 3], bbox[:, :, 2]], dim=-1)[:, :, None, :]   # w, h
+    scale = torch.tensor([float(mw), float(mh)], device=frame_keypoints.device, dtype=frame_keypoints.dtype)
+    return (frame_keypoints - offset) / size * scale

@@ -15,6 +15,22 @@ class HeatmapLabeledBatchDict(TypedDict):
     idxs: torch.Tensor
 
 
+class MultiviewHeatmapLabeledBatchDict(TypedDict, total=False):
+    images: torch.Tensor      # (B, V, 3, H, W)
+    keypoints: torch.Tensor   # (B, 2 V K) model px
+    heatmaps: torch.Tensor    # (B, V K, h, w)
+    bbox: torch.Tensor        # (B, 4V)   [x, y, h, w] per view
+    idxs: torch.Tensor
+    num_views: torch.Tensor   # (B,)
+    concat_order: list
+    view_names: list
+    # present when camera calibration is available ((B, 1) placeholders otherwise, as in the reference)
+    keypoints_3d: torch.Tensor       # (B, K, 3)
+    intrinsic_matrix: torch.Tensor   # (B, V, 3, 3)
+    extrinsic_matrix: torch.Tensor   # (B, V, 3, 4)
+    distortions: torch.Tensor        # (B, V, 4 | 5 | 8 | 12) OpenCV order
+
+
 class UnlabeledBatchDict(TypedDict):
     frames: torch.Tensor      # (S, 3, H, W)
     transforms: torch.Tensor  # (2, 3) | (S, 2, 3) | (1,) sentinel

@@ -8,14 +8,15 @@ import numpy as np
 import torch
 
 from .. import ops
-from .losses import HeatmapJSLoss, HeatmapKLLoss, HeatmapMSELoss, Loss, PCALoss, TemporalHeatmapLoss, TemporalLoss, UnimodalLoss
+from .losses import (HeatmapJSLoss, HeatmapKLLoss, HeatmapMSELoss, Loss, PairwiseProjectionsLoss, PCALoss, ReprojectionHeatmapLoss,
+                     TemporalHeatmapLoss, TemporalLoss, UnimodalLoss)
 
 _HEATMAP_LOSSES = ("heatmap_mse", "heatmap_kl", "heatmap_js")
 
 
 def get_loss_classes() -> dict[str, type[Loss]]:
-    """Loss name -> class (reference :73-91).  Names outside the heatmap-tracker hot path (regression, the 3-D supervised losses)
-    are not registered here; ``unimodal_mse`` is added."""
+    """Loss name -> class (reference :73-91).  Names outside the heatmap-tracker hot path (regression) are not registered here;
+    ``unimodal_mse`` is added."""
     return {
         HeatmapMSELoss.loss_name: HeatmapMSELoss,
         HeatmapKLLoss.loss_name: HeatmapKLLoss,
@@ -26,6 +27,8 @@ def get_loss_classes() -> dict[str, type[Loss]]:
         TemporalHeatmapLoss.LOSS_NAME_MSE: TemporalHeatmapLoss,
         TemporalHeatmapLoss.LOSS_NAME_KL: TemporalHeatmapLoss,
         UnimodalLoss.loss_name: UnimodalLoss,
+        PairwiseProjectionsLoss.loss_name: PairwiseProjectionsLoss,
+        ReprojectionHeatmapLoss.loss_name: ReprojectionHeatmapLoss,
     }
 
 
@@ -76,6 +79,20 @@ def get_loss_factories(cfg: Any, data_module: Any) -> dict[str, LossFactory]:
     if str(model["model_type"]).find("heatmap") == -1:
         raise NotImplementedError("only heatmap trackers are implemented on the MI355X path")
     params["supervised"]["heatmap_" + str(_get(model, "heatmap_loss_type", "mse"))] = {"log_weight": 0.0}
+    # the calibrated 3-D losses: a multi-view model, a camera parameter file and the loss's log_weight in the config (reference :117-143)
+    if str(model["model_type"]).find("multiview") > -1 and _get(data, "camera_params_file"):
+        log_weight_sp = _get(_get(losses, "supervised_pairwise_projections", None) or {}, "log_weight")
+        if log_weight_sp is not None:
+            params["supervised"]["supervised_pairwise_projections"] = {"log_weight": log_weight_sp}
+        log_weight_hr = _get(_get(losses, "supervised_reprojection_heatmap_mse", None) or {}, "log_weight")
+        if log_weight_hr is not None:
+            dims = _get(data, "image_resize_dims")
+            height_og, width_og = dims["height"], dims["width"]
+            ds = _get(data, "downsample_factor", 2)
+            params["supervised"]["supervised_reprojection_heatmap_mse"] = {
+                "log_weight": log_weight_hr, "original_image_height": height_og, "original_image_width": width_og,
+                "downsampled_image_height": int(height_og // (2 ** ds)), "downsampled_image_width": int(width_og // (2 ** ds)),
+            }
     losses_to_use = _get(model, "losses_to_use", None)
     for loss_name in (losses_to_use or []):
         if loss_name == "":

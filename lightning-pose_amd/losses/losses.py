@@ -18,7 +18,8 @@ import torch
 from .. import ops
 from ..utils.pca import KeypointPCA
 
-__all__ = ["Loss", "HeatmapLoss", "HeatmapMSELoss", "TemporalLoss", "TemporalHeatmapLoss", "PCALoss", "UnimodalLoss", "RegressionRMSELoss"]
+__all__ = ["Loss", "HeatmapLoss", "HeatmapMSELoss", "TemporalLoss", "TemporalHeatmapLoss", "PCALoss", "UnimodalLoss", "RegressionRMSELoss",
+           "PairwiseProjectionsLoss", "ReprojectionHeatmapLoss"]
 
 _DEFAULT_TORCH_DEVICE = "cpu"
 if torch.cuda.is_available():
@@ -249,4 +250,62 @@ class RegressionRMSELoss(Loss):
     def __call__(self, keypoints_targ: torch.Tensor, keypoints_pred: torch.Tensor,
                  stage: Literal["train", "val", "test"] | None = None, **kwargs: Any):
         scalar_loss = ops.rmse(keypoints_targ, keypoints_pred)
+        return scalar_loss, self.log_loss(loss=scalar_loss, stage=stage)
+
+
+class PairwiseProjectionsLoss(Loss):
+    """Penalize projections from each pair of cameras into 3D world space (reference :999-1126): mean over the (sample, pair, keypoint)
+    whose 3-D target and prediction are both free of NaN of ``||target - prediction||_2``; 0 (with a zero gradient) if none is.  One launch
+    for value and gradient; the number of valid entries is never read by the host."""
+
+    loss_name = "supervised_pairwise_projections"
+
+    def __init__(self, log_weight: float = 0.0, **kwargs: Any) -> None:
+        super().__init__(log_weight=log_weight)
+
+    def __call__(self, keypoints_targ_3d: torch.Tensor, keypoints_pred_3d: torch.Tensor,
+                 stage: Literal["train", "val", "test"] | None = None, **kwargs: Any):
+        if keypoints_targ_3d is None or keypoints_pred_3d is None:
+            raise ValueError(
+                f"3D keypoints not available for {stage} stage. "
+                "Camera params file is required but not found;"
+                "Turn off supervised_pairwise_projections loss to avoid this error."
+            )
+        scalar_loss = ops.pairwise_projections_loss(keypoints_targ_3d, keypoints_pred_3d)
+        return scalar_loss, self.log_loss(loss=scalar_loss, stage=stage)
+
+
+class ReprojectionHeatmapLoss(Loss):
+    """Penalize error between predicted 2D->3D->2D->heatmap and ground truth heatmap (reference :1129-1260): Gaussian maps drawn at the
+    reprojected keypoints (gradient kept) against the target maps, the squared error averaged over the maps whose target is not all zero -
+    ``ops.generate_heatmaps_with_grad`` and ``ops.heatmap_mse``, which own that mask - times the reference's scale (see ``__call__``)."""
+
+    loss_name = "supervised_reprojection_heatmap_mse"
+
+    def __init__(self, original_image_height: int, original_image_width: int, downsampled_image_height: int, downsampled_image_width: int,
+                 log_weight: float = 0.0, **kwargs: Any) -> None:
+        super().__init__(log_weight=log_weight)
+        self.original_image_height = original_image_height
+        self.original_image_width = original_image_width
+        self.downsampled_image_height = downsampled_image_height
+        self.downsampled_image_width = downsampled_image_width
+
+    def __call__(self, heatmaps_targ: torch.Tensor, keypoints_pred_2d_reprojected: torch.Tensor,
+                 stage: Literal["train", "val", "test"] | None = None, **kwargs: Any):
+        if keypoints_pred_2d_reprojected is None:
+            raise ValueError(
+                f"Reprojected keypoints not available for {stage} stage. "
+                "Camera params file is required but not found;"
+                "Turn off supervised_reprojection_heatmap loss to avoid this error."
+            )
+        heatmaps_pred = ops.generate_heatmaps_with_grad(
+            keypoints_pred_2d_reprojected, self.original_image_height, self.original_image_width,
+            (self.downsampled_image_height, self.downsampled_image_width))
+        # ops.heatmap_mse scales by the h * w pixels of a map.  The reference's compute_loss (:1209-1212) reads "h" and "w" from dimensions
+        # 1 and 2 of the tensors its __call__ hands it, which are (batch, keypoints, h, w): its scale is keypoints * h.  Kept, value for value.
+        _, k, h, w = heatmaps_targ.shape
+        scalar_loss = ops.heatmap_mse(heatmaps_targ, heatmaps_pred) * (float(k * h) / float(h * w))
+        # no labelled map at all: the reference's remove_nans (:1188-1191) returns 0 where heatmap_mse's mean of nothing is NaN (its backward
+        # already writes zeros then); decided on the device, nothing is read back
+        scalar_loss = torch.where((heatmaps_targ != 0).any(), scalar_loss, torch.zeros_like(scalar_loss))
         return scalar_loss, self.log_loss(loss=scalar_loss, stage=stage)

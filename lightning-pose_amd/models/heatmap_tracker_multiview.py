@@ -9,9 +9,14 @@ attributes (``num_views``, ``view_embeddings``, ``head``, ``rmse_loss``), ``stat
 :class:`lightning_pose_amd.vit_engine.ViTEngine` (``lp_vit_mv_tokens_fwd`` / ``_bwd`` for the token assembly, every other kernel shared with
 the single-view ViT tracker), and decode / affine-undo / bounding-box maps are the fused decode of :class:`HeatmapTracker`.
 
+Calibrated rigs: when the labeled batch carries ``keypoints_3d`` (last dimension 3) with ``intrinsic_matrix``, ``extrinsic_matrix`` and
+``distortions``, ``get_loss_inputs_labeled`` triangulates the predicted keypoints from every camera pair (``keypoints_pred_3d``) and - when
+``supervised_reprojection_heatmap_mse`` is configured - reprojects the mean of the pairs into every view in model px
+(``keypoints_pred_2d_reprojected``): one launch forward and one backward (``ops.camera_chain``, ``csrc/cameras.hip``) in place of the
+reference's Python loop over pairs and samples.  The batch dict is where this starts: the calibration-file loader (``CameraGroup``) is not part
+of this package.
+
 Outside this path (each raises where a configuration asks for it):
-* the calibrated 3-D supervised losses ``supervised_pairwise_projections`` / ``supervised_reprojection_heatmap_mse`` and the camera
-  projection code behind them (``data/cameras.py``): the three 3-D keys of the labeled outputs are always ``None``;
 * the ``PatchMasking`` curriculum callback;
 * the DINOv2 / DINOv3 / MAE ("vitb_imagenet") backbones of the reference's multi-view list: ``vits_dino`` and ``vitb_dino`` are implemented.
 """
@@ -22,6 +27,9 @@ from typing import Any, Literal
 
 import torch
 
+from .. import ops
+from ..data.bboxes import model_dims
+from ..losses.losses import PairwiseProjectionsLoss, ReprojectionHeatmapLoss
 from .backbones.factory import VIT_CONFIGS
 from .base import SemiSupervisedTrackerMixin
 from .datatypes import HeatmapTrackerMultiviewTransformerLabeledOutputsDict, HeatmapTrackerUnlabeledOutputsDict
@@ -31,7 +39,7 @@ from .heatmap_tracker import HeatmapTracker
 _REFERENCE_MULTIVIEW_BACKBONES = ("vits_dino", "vits_dinov2", "vits_dinov3", "vitb_dino", "vitb_dinov2", "vitb_dinov3", "vitb_imagenet")
 # ... of which this package implements
 ALLOWED_TRANSFORMER_BACKBONES_MULTIVIEW = tuple(b for b in _REFERENCE_MULTIVIEW_BACKBONES if b in VIT_CONFIGS)
-_CALIBRATED_LOSSES = ("supervised_pairwise_projections", "supervised_reprojection_heatmap_mse")
+_CALIBRATED_LOSSES = {"supervised_pairwise_projections": PairwiseProjectionsLoss, "supervised_reprojection_heatmap_mse": ReprojectionHeatmapLoss}
 
 
 class BackboneNotImplementedError(NotImplementedError, ValueError):
@@ -58,9 +66,13 @@ class HeatmapTrackerMultiviewTransformer(HeatmapTracker):
             raise NotImplementedError(f"{head} is not a valid multiview transformer head")
         if int(num_views) < 1:
             raise ValueError(f"num_views must be a positive number of camera views, got {num_views}")
-        asked = [n for n in _CALIBRATED_LOSSES if n in getattr(loss_factory, "loss_instance_dict", {})]
+        # the calibrated 3-D losses are this package's own classes (their inputs come from the fused geometry kernel); anything else under
+        # those names - the reference's torch implementation, a stand-in - is refused rather than fed
+        registered = getattr(loss_factory, "loss_instance_dict", {})
+        asked = [n for n, cls in _CALIBRATED_LOSSES.items() if n in registered and type(registered[n]) is not cls]
         if asked:
-            raise NotImplementedError(f"the calibrated 3-D supervised losses {asked} (camera projection) are outside the MI355X path")
+            raise NotImplementedError(f"the calibrated 3-D supervised losses {asked} (camera projection) are outside the MI355X path unless they "
+                                      "are lightning_pose_amd.losses.losses.PairwiseProjectionsLoss / ReprojectionHeatmapLoss")
         self.num_views = int(num_views)   # (read by _vit_engine_extras while HeatmapTracker.__init__ builds the engine)
         super().__init__(num_keypoints=num_keypoints, loss_factory=loss_factory, backbone=backbone, downsample_factor=downsample_factor,
                          pretrained=pretrained, torch_seed=torch_seed, optimizer=optimizer, optimizer_params=optimizer_params,
@@ -91,10 +103,24 @@ class HeatmapTrackerMultiviewTransformer(HeatmapTracker):
         return super().forward(images)
 
     def get_loss_inputs_labeled(self, batch_dict: dict) -> HeatmapTrackerMultiviewTransformerLabeledOutputsDict:
-        """Predicted heat-maps and keypoints (frame px); the 3-D projection keys need camera calibration code that is outside this path
-        and stay ``None`` (reference :250-314: ``None`` whenever the batch carries no calibration)."""
+        """Predicted heat-maps and keypoints (frame px) and, for a calibrated batch, the 3-D keys (reference :250-314: ``None`` whenever the
+        batch carries no calibration; the reprojection only when its loss is configured)."""
         out = super().get_loss_inputs_labeled(batch_dict)
-        return {**out, "keypoints_targ_3d": None, "keypoints_pred_3d": None, "keypoints_pred_2d_reprojected": None}
+        targ_3d = pred_3d = reprojected = None
+        if "keypoints_3d" in batch_dict and batch_dict["keypoints_3d"].shape[-1] == 3:
+            pred = out["keypoints_pred"]
+            views = batch_dict["images"].shape[1]
+            k = pred.shape[1] // 2 // views
+            points = pred.reshape(-1, views, k, 2)
+            rig = (batch_dict["intrinsic_matrix"].float(), batch_dict["extrinsic_matrix"].float(), batch_dict["distortions"].float())
+            targ_3d = batch_dict["keypoints_3d"]
+            if "supervised_reprojection_heatmap_mse" in getattr(self.loss_factory, "loss_instance_dict", {}):
+                mh, mw = model_dims(batch_dict)
+                pred_3d, reprojected = ops.camera_chain(points, *rig, batch_dict["bbox"], mh, mw)
+                reprojected = reprojected.reshape(-1, views * k, 2)
+            else:
+                pred_3d = ops.camera_pairs_to_3d(points, *rig)
+        return {**out, "keypoints_targ_3d": targ_3d, "keypoints_pred_3d": pred_3d, "keypoints_pred_2d_reprojected": reprojected}
 
     def get_parameters(self) -> list[dict]:
         """Order matters: UnfreezeBackbone requires group 0 = backbone, group 1 = head; view_embeddings follow (reference :352-367)."""

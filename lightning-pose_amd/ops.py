@@ -555,6 +555,158 @@ def rmse(keypoints_targ: torch.Tensor, keypoints_pred: torch.Tensor) -> torch.Te
     return loss.reshape(())
 
 
+# --------------------------------------------------------------------------------------------------------
+# camera geometry of the calibrated multi-view losses (csrc/cameras.hip)
+# --------------------------------------------------------------------------------------------------------
+
+def _cam_dist12(dist: torch.Tensor) -> torch.Tensor:
+    """(B, V, n) OpenCV distortion parameters, n in {4, 5, 8, 12, 14} -> (B, V, 12) fp32, missing ones 0.  The tilt pair of a 14-parameter
+    set is not modelled: it must be zero (checked here, a host read that only such sets pay)."""
+    n = dist.shape[-1]
+    if n not in (4, 5, 8, 12, 14):
+        raise ValueError(f"distortion parameters must number 4, 5, 8, 12 or 14 (OpenCV order), got {n}")
+    d = _f32c(dist)
+    if n == 14:
+        if bool((d[..., 12:] != 0).any()):
+            raise NotImplementedError("the tilted-sensor distortion parameters (tau_x, tau_y) are not implemented")
+        d = d[..., :12]
+    if d.shape[-1] < 12:
+        d = torch.nn.functional.pad(d, (0, 12 - d.shape[-1]))
+    return d.contiguous()
+
+
+def _cam_rig(intrinsics: torch.Tensor, extrinsics: torch.Tensor, dist: torch.Tensor, b: int):
+    if intrinsics.dim() != 4 or intrinsics.shape[0] != b or tuple(intrinsics.shape[2:]) != (3, 3):
+        raise ValueError(f"intrinsics must be (batch = {b}, num_views, 3, 3), got {tuple(intrinsics.shape)}")
+    v = int(intrinsics.shape[1])
+    if tuple(extrinsics.shape) != (b, v, 3, 4):
+        raise ValueError(f"extrinsics must be {(b, v, 3, 4)}, got {tuple(extrinsics.shape)}")
+    if dist.dim() != 3 or tuple(dist.shape[:2]) != (b, v):
+        raise ValueError(f"dist must be {(b, v)} + (num_params,), got {tuple(dist.shape)}")
+    return _f32c(intrinsics), _f32c(extrinsics), _cam_dist12(dist), v
+
+
+def _cam_bbox(bbox: torch.Tensor | None, b: int, v: int, dev: torch.device) -> torch.Tensor | None:
+    if bbox is None:
+        return None
+    bb = _f32c(bbox).to(dev)
+    if tuple(bb.shape) != (b, 4 * v):
+        raise ValueError(f"bbox must be {(b, 4 * v)} ([x, y, h, w] per view), got {tuple(bb.shape)}")
+    return bb
+
+
+class _CamChainFn(torch.autograd.Function):
+    """points (B, V, K, 2) -> p3d (B, P, K, 3) [, p2d (B, V, K, 2)]: lp_cam_chain_fwd / _bwd, one launch each"""
+
+    @staticmethod
+    def forward(ctx, points, intr, extr, dist12, bbox, mh, mw, want_2d):
+        require_device(points, intr, extr, dist12, bbox)
+        pts = _f32c(points)
+        b, v, k, _ = pts.shape
+        npairs = v * (v - 1) // 2
+        p3d = torch.empty(b, npairs, k, 3, device=pts.device, dtype=torch.float32)
+        p2d = torch.empty(b, v, k, 2, device=pts.device, dtype=torch.float32) if want_2d else None
+        check(_lib.lib().lp_cam_chain_fwd(_p(pts), _p(intr), _p(extr), _p(dist12), _p(bbox), mh, mw, b, v, k, _p(p3d), _p(p2d), _stream()),
+              "lp_cam_chain_fwd")
+        ctx.save_for_backward(pts, intr, extr, dist12, p3d)
+        ctx.bbox, ctx.args, ctx.in_dtype = bbox, (mh, mw), points.dtype
+        ctx.set_materialize_grads(False)
+        return p3d, p2d
+
+    @staticmethod
+    def backward(ctx, g3d, g2d):
+        if g3d is None and g2d is None:
+            return (None,) * 8
+        pts, intr, extr, dist12, p3d = ctx.saved_tensors
+        b, v, k, _ = pts.shape
+        g3d = _f32c(g3d) if g3d is not None else None
+        g2d = _f32c(g2d) if g2d is not None else None
+        nws = int(_lib.lib().lp_cam_chain_workspace_bytes(b, v, k))
+        ws = torch.empty(nws, device=pts.device, dtype=torch.uint8)
+        gpts = torch.empty_like(pts)
+        mh, mw = ctx.args
+        check(_lib.lib().lp_cam_chain_bwd(_p(pts), _p(intr), _p(extr), _p(dist12), _p(ctx.bbox), mh, mw, b, v, k, _p(p3d), _p(g3d), _p(g2d),
+                                          _p(ws), nws, _p(gpts), _stream()), "lp_cam_chain_bwd")
+        return gpts.to(ctx.in_dtype), None, None, None, None, None, None, None
+
+
+def _cam_points(points: torch.Tensor) -> tuple[int, int, int]:
+    if points.dim() != 4 or points.shape[-1] != 2 or points.shape[1] < 2:
+        raise ValueError(f"points must be (batch, num_views >= 2, num_keypoints, 2), got {tuple(points.shape)}")
+    return int(points.shape[0]), int(points.shape[1]), int(points.shape[2])
+
+
+def camera_pairs_to_3d(points: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor, dist: torch.Tensor) -> torch.Tensor:
+    """Triangulate every camera pair: points (B, V, K, 2) frame px -> (B, V (V - 1) / 2, K, 3); differentiable in the points."""
+    b, v, _ = _cam_points(points)
+    intr, extr, d12, v2 = _cam_rig(intrinsics, extrinsics, dist, b)
+    if v2 != v:
+        raise ValueError(f"{v} views of points, {v2} cameras")
+    return _CamChainFn.apply(points, intr, extr, d12, None, 1.0, 1.0, False)[0]
+
+
+def camera_chain(points: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor, dist: torch.Tensor, bbox: torch.Tensor | None,
+                 model_h: float, model_w: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """The geometry of both calibrated losses in one launch (and one backward): every pair's triangulation (B, P, K, 3), and their mean
+    reprojected into every view, distorted and mapped to model px with ``bbox`` (B, 4 V) (frame px if None) -> (B, V, K, 2)."""
+    b, v, _ = _cam_points(points)
+    intr, extr, d12, v2 = _cam_rig(intrinsics, extrinsics, dist, b)
+    if v2 != v:
+        raise ValueError(f"{v} views of points, {v2} cameras")
+    return _CamChainFn.apply(points, intr, extr, d12, _cam_bbox(bbox, b, v, points.device), float(model_h), float(model_w), True)
+
+
+class _CamProjectFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p3, intr, extr, dist12, bbox, mh, mw):
+        require_device(p3, intr, extr, dist12, bbox)
+        x = _f32c(p3)
+        b, k, _ = x.shape
+        v = intr.shape[1]
+        out = torch.empty(b, v, k, 2, device=x.device, dtype=torch.float32)
+        check(_lib.lib().lp_cam_project_fwd(_p(x), _p(intr), _p(extr), _p(dist12), _p(bbox), mh, mw, b, v, k, _p(out), _stream()),
+              "lp_cam_project_fwd")
+        ctx.save_for_backward(x, intr, extr, dist12)
+        ctx.bbox, ctx.args, ctx.in_dtype = bbox, (mh, mw), p3.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, intr, extr, dist12 = ctx.saved_tensors
+        b, k, _ = x.shape
+        v = intr.shape[1]
+        mh, mw = ctx.args
+        gx = torch.empty_like(x)
+        check(_lib.lib().lp_cam_project_bwd(_p(x), _p(intr), _p(extr), _p(dist12), _p(ctx.bbox), mh, mw, b, v, k, _p(_f32c(g)), _p(gx),
+                                            _stream()), "lp_cam_project_bwd")
+        return gx.to(ctx.in_dtype), None, None, None, None, None, None
+
+
+def camera_project(points_3d: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor, dist: torch.Tensor,
+                   bbox: torch.Tensor | None = None, model_h: float = 1.0, model_w: float = 1.0) -> torch.Tensor:
+    """points_3d (B, K, 3) -> (B, V, K, 2) in every view (frame px; model px with ``bbox``); differentiable in the points."""
+    if points_3d.dim() != 3 or points_3d.shape[-1] != 3:
+        raise ValueError(f"points_3d must be (batch, num_keypoints, 3), got {tuple(points_3d.shape)}")
+    b = int(points_3d.shape[0])
+    intr, extr, d12, v = _cam_rig(intrinsics, extrinsics, dist, b)
+    return _CamProjectFn.apply(points_3d, intr, extr, d12, _cam_bbox(bbox, b, v, points_3d.device), float(model_h), float(model_w))
+
+
+def pairwise_projections_loss(keypoints_targ_3d: torch.Tensor, keypoints_pred_3d: torch.Tensor) -> torch.Tensor:
+    """mean over the valid (sample, pair, keypoint) of ||target - prediction||_2 (reference losses/losses.py:1036-1126); value and gradient
+    in one launch, the number of valid entries never read by the host."""
+    require_device(keypoints_targ_3d, keypoints_pred_3d)
+    targ, pred = _f32c(keypoints_targ_3d), _f32c(keypoints_pred_3d)
+    if pred.dim() != 4 or pred.shape[-1] != 3 or tuple(targ.shape) != (pred.shape[0], pred.shape[2], 3):
+        raise ValueError(f"pairwise projections: predictions {tuple(pred.shape)} must be (B, pairs, K, 3) and targets (B, K, 3), got "
+                         f"{tuple(targ.shape)}")
+    b, npairs, k, _ = pred.shape
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    grad = torch.empty_like(pred)
+    check(_lib.lib().lp_cam_pairwise_fwd_bwd(_p(targ), _p(pred), b, npairs, k, _p(loss), _p(grad), _stream()), "lp_cam_pairwise_fwd_bwd")
+    return _UnitGradFn.apply(keypoints_pred_3d, loss.reshape(()), grad)
+
+
 class _LossCombineFn(torch.autograd.Function):
     """weighted[i] = w[i] * x[i];  total = sum_i a[i] * weighted[i]  (csrc/kploss.hip: lp_loss_combine, one launch each way)"""
 
