@@ -50,8 +50,9 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * not only when symbols come or go.  lp_version() returns the value the library was built with; a caller compares the two before its first
  * call (lightning_pose_amd/_lib.py raises LpHipUnavailable on a mismatch) - a library built against an older header would otherwise take,
  * e.g., the stream argument for an inserted flag without any error.  History: 131 = round 5 (decode `prune`, bn_bwd `terms_ws`), 140 = round 6,
- * 144 = the multi-view token assembly (lp_vit_mv_tokens_*), 145 = the camera geometry of the calibrated 3-D losses (lp_cam_*). */
-#define LP_HIP_ABI_VERSION 145
+ * 144 = the multi-view token assembly (lp_vit_mv_tokens_*), 145 = the camera geometry of the calibrated 3-D losses (lp_cam_*),
+ * 146 = patch masking (lp_patch_mask_f32). */
+#define LP_HIP_ABI_VERSION 146
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -689,6 +690,27 @@ int lp_labelaug_finish(const void* src_u8, int B, int Hs, int Ws, const lp_label
  * LP_AUG_ELASTIC when field != NULL (first-order inverse of the elastic map).  NaN stays NaN.  kp_out must not alias kp. */
 int lp_labelaug_keypoints(const float* kp, int B, int K, const float* affine, const lp_labelaug_image* params, const float* field, int H,
                           int W, float* kp_out, lp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Patch masking (csrc/patchmask.hip): the multi-view transformer's masking curriculum (callbacks.py:279-401, PatchMasker) - choose
+ * `count` patches per image and zero them, ONE launch for the batch, no workspace, nothing read back.
+ * images / out: fp32 (BV, C, H, W) contiguous, BV = samples x views.  Patch grid nh = H / patch, nw = W / patch (floor), N = nh nw; patch p
+ * covers rows (p / nw) patch ... and columns (p % nw) patch ...; pixels beyond nh patch / nw patch are never masked.
+ * mask_in == NULL: word(i, p) = the first output word of Philox4x32-10 with key `key` and counter (p, i, 0, 0); patch p of image i is masked
+ *   iff its rank among the N pairs (word, p) in ascending lexicographic order is < count: exactly `count` patches per image for any N, a
+ *   function of (key, i, p) only - never of the launch geometry.  The caller packs key = (seed mod 2^32) | (step mod 2^32) << 32.  Unlike the
+ *   reference's generator seed (patch_seed + step + 1000 b + 100 v, which step 100 of sample 0 shares with step 0 of view 1), two different
+ *   (step, sample, view) never share a stream.
+ * mask_in != NULL: (BV, N) fp32, 0 = mask, anything else = keep; used as given, `count` is ignored.
+ * mask_out (BV, N): 1.0f (kept) or 0.0f (masked).  out: every pixel of a masked patch, in all C channels, is +0.0f whatever it held (NaN and
+ * Inf included); every other pixel is copied bit for bit (NaN payloads, -0.0).  out == images (in place) is allowed and gives the same
+ * bits; any other overlap is not.  `images` is otherwise not written.
+ * LP_ERR_UNSUPPORTED: N > 1024 (512 x 512 at patch 16 is the largest square grid) or BV > 65535.  LP_ERR_ARGUMENT: a null images / out /
+ * mask_out, H < patch or W < patch, count outside [0, N].  Any H, W: 16-byte accesses when W % 4 == 0, patch % 4 == 0 and both pointers
+ * are 16-byte aligned, 4-byte ones otherwise.
+ * ------------------------------------------------------------------------------------------------------ */
+int lp_patch_mask_f32(const float* images, int BV, int C, int H, int W, int patch, int count, unsigned long long key, const float* mask_in,
+                      float* out, float* mask_out, lp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Optimiser: torch.optim.Adam / AdamW semantics (models/base.py:458-479) over one flat fp32 range, also emitting

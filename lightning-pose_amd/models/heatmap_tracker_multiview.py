@@ -16,8 +16,10 @@ Calibrated rigs: when the labeled batch carries ``keypoints_3d`` (last dimension
 reference's Python loop over pairs and samples.  The batch dict is where this starts: the calibration-file loader (``CameraGroup``) is not part
 of this package.
 
+The ``PatchMasking`` curriculum the reference trains this model with is ``lightning_pose_amd.callbacks.PatchMasking``
+(``callbacks.get_patch_masking_callback(cfg)`` builds it under the reference's condition).
+
 Outside this path (each raises where a configuration asks for it):
-* the ``PatchMasking`` curriculum callback;
 * the DINOv2 / DINOv3 / MAE ("vitb_imagenet") backbones of the reference's multi-view list: ``vits_dino`` and ``vitb_dino`` are implemented.
 """
 

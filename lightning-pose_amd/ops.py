@@ -20,7 +20,7 @@ from ._lib import LpHipUnavailable, check
 
 __all__ = [
     "decode", "DecodeFrameMap", "generate_heatmaps", "heatmap_mse", "unimodal_mse", "temporal_loss", "pca_loss",
-    "rmse", "require_device", "frames_resize", "frames_augment", "labeled_keypoints",
+    "rmse", "require_device", "frames_resize", "frames_augment", "labeled_keypoints", "patch_mask",
 ]
 
 
@@ -955,3 +955,46 @@ def labelaug_keypoints(keypoints: torch.Tensor, affine: torch.Tensor | None, tab
     check(_lib.lib().lp_labelaug_keypoints(_p(kp), b, k, _p(aff), _p(table), _p(f), int(h), int(w), _p(out), _stream()),
           "lp_labelaug_keypoints")
     return out
+
+
+# --------------------------------------------------------------------------------------------------------
+# patch masking (csrc/patchmask.hip): the multi-view transformer's curriculum, one launch per batch
+# --------------------------------------------------------------------------------------------------------
+
+PATCH_MASK_MAX_PATCHES = 1024   # csrc/patchmask.hip: kPatchMaskMaxN
+
+
+def patch_mask_key(seed: int, step: int) -> int:
+    """the Philox key of a (seed, training step): (seed mod 2^32) | (step mod 2^32) << 32"""
+    return (int(seed) & 0xFFFFFFFF) | ((int(step) & 0xFFFFFFFF) << 32)
+
+
+def patch_mask(images: torch.Tensor, key: int | tuple[int, int], count: int, patch: int = 16,
+               mask: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``images`` (B, V, C, H, W) fp32 -> (the images with ``count`` patches of every view set to +0.0, the (B, V, N) fp32 mask of 1 = kept /
+    0 = masked), N = (H // patch) * (W // patch).  ``key``: the 64-bit Philox key, or ``(seed, step)`` for ``patch_mask_key``.  The choice is
+    the rank rule of include/lp_hip.h (lp_patch_mask_f32): a function of (key, b * V + v, patch) alone.  ``mask`` (B, V, N), 0 = mask: used
+    as given instead of choosing, ``count`` is then ignored.  One launch, nothing comes back to the host; ``images`` is not written."""
+    assert not images.requires_grad, "patch_mask has no backward: images carry no gradient"
+    require_device(images, mask)
+    if images.dim() != 5 or images.dtype != torch.float32:
+        raise ValueError(f"images must be fp32 (B, V, C, H, W), got {images.dtype} {tuple(images.shape)}")
+    b, v, c, h, w = images.shape
+    patch = int(patch)
+    n = (h // patch) * (w // patch) if patch > 0 else 0
+    if n > PATCH_MASK_MAX_PATCHES:
+        raise NotImplementedError(f"patch_mask: {h} x {w} px at patch {patch} is {n} patches per view; the kernel ranks at most "
+                                  f"{PATCH_MASK_MAX_PATCHES} (512 x 512 px at patch 16)")
+    x = images.contiguous()
+    given = None
+    if mask is not None:
+        if tuple(mask.shape) != (b, v, n):
+            raise ValueError(f"mask must be (B, V, N) = {(b, v, n)}, got {tuple(mask.shape)}")
+        given = _f32c(mask)
+    if isinstance(key, tuple):
+        key = patch_mask_key(*key)
+    out = torch.empty_like(x)
+    mask_out = torch.empty(b, v, n, device=x.device, dtype=torch.float32)
+    check(_lib.lib().lp_patch_mask_f32(_p(x), b * v, c, h, w, patch, int(count), int(key) & 0xFFFFFFFFFFFFFFFF, _p(given), _p(out), _p(mask_out),
+                                       _stream()), "lp_patch_mask_f32")
+    return out, mask_out

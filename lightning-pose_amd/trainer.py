@@ -2,7 +2,7 @@
 
 Order per batch (reference: Lightning 2.5 fit loop as used by train.py:411-431): callbacks.on_train_batch_start ->
 training_step -> backward -> gradient all-reduce -> optimizer.step -> zero_grad; per epoch: on_train_epoch_start ...
-lr_scheduler.step().  The module is anything with the LightningModule surface of models/base.py.
+on_train_epoch_end (after the epoch's validation) -> lr_scheduler.step().  The module is anything with the LightningModule surface of models/base.py.
 """
 
 from __future__ import annotations
@@ -38,6 +38,12 @@ class Trainer:
         self.dp: DataParallel | None = None
         self.logged_history: list[dict[str, float]] = []
         self.validation_history: list[dict[str, float]] = []
+        self._module = None                   # the module being fitted (setup)
+
+    @property
+    def global_step(self) -> int:
+        """Lightning's ``trainer.global_step``: the optimiser steps the fitted module has taken (0 before ``setup``)"""
+        return int(self._module.global_step) if self._module is not None else 0
 
     def _hook(self, name: str, *args: Any) -> None:
         for cb in self.callbacks:
@@ -48,6 +54,7 @@ class Trainer:
     def setup(self, model) -> None:
         import torch.distributed as dist
 
+        self._module = model
         if self.dp is None:
             want = self._want_dp if self._want_dp is not None else dist.is_initialized()
             self.dp = DataParallel(model.net, sync_bn=self.sync_batchnorm) if want else None
@@ -180,4 +187,5 @@ class Trainer:
                     break
             if val_batches is not None:  # check_val_every_n_epoch = 1
                 self.validate(model, val_batches(epoch))
+            self._hook("on_train_epoch_end", model)   # Lightning's order: after the epoch's validation, before the scheduler
             self.scheduler.step()
