@@ -51,8 +51,8 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * call (lightning_pose_amd/_lib.py raises LpHipUnavailable on a mismatch) - a library built against an older header would otherwise take,
  * e.g., the stream argument for an inserted flag without any error.  History: 131 = round 5 (decode `prune`, bn_bwd `terms_ws`), 140 = round 6,
  * 144 = the multi-view token assembly (lp_vit_mv_tokens_*), 145 = the camera geometry of the calibrated 3-D losses (lp_cam_*),
- * 146 = patch masking (lp_patch_mask_f32). */
-#define LP_HIP_ABI_VERSION 146
+ * 146 = patch masking (lp_patch_mask_f32), 147 = LayerScale inside the LayerNorm walks (lp_layernorm_ls_*, the DINOv2 backbones). */
+#define LP_HIP_ABI_VERSION 147
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -402,6 +402,12 @@ int lp_f32_layernorm_fwd(const float* x, const float* delta, float* x_out, const
                          int drop_T, float* y, float* mean, float* rstd, lp_stream_t stream);
 int lp_f32_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, int M, int D, int drop_T,
                          float* dx_acc, float* dgamma_acc, float* dbeta_acc, lp_stream_t stream);
+/* the fp32 forms of lp_layernorm_ls_fwd / _bwd (below): delta / branch / dy fp32, dx_out = ls o (updated dx_acc) unrounded */
+int lp_f32_layernorm_ls_fwd(const float* x, const float* delta, const float* ls, float* x_out, const float* gamma, const float* beta, float eps,
+                            int M, int D, int drop_T, float* y, float* mean, float* rstd, lp_stream_t stream);
+int lp_f32_layernorm_ls_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
+                            const float* branch, int M, int D, int drop_T, float* dx_acc, float* dx_out, float* dgamma_acc, float* dbeta_acc,
+                            float* colsum_acc, float* dls_acc, lp_stream_t stream);
 int lp_f32_gelu_fwd(const float* x, size_t n, float* y, lp_stream_t stream);
 int lp_f32_gelu_bwd(const float* x, const float* dy, size_t n, float* dx, lp_stream_t stream);
 int lp_f32_attn_fwd(const float* qkv, int ld, int k_off, int v_off, int B, int nh, int T, float scale, float* p, float* o, int ldo,
@@ -579,6 +585,20 @@ int lp_gelu_bwd_colsum(const void* x_bf16, const void* dy_bf16, int rows, int co
 int lp_layernorm_bwd_bf16_colsum(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma, int M, int D,
                                  int drop_T, float* dx_acc, void* dx_bf16, float* dgamma_acc, float* dbeta_acc, float* colsum_acc,
                                  lp_stream_t stream);
+/* LayerScale (transformers Dinov2LayerScale: a learned per-channel factor on each branch output, in front of the residual add) inside the
+ * two LayerNorm walks that already touch those tensors - the DINOv2 backbones ("vits_dinov2" / "vitb_dinov2").
+ * forward: lp_layernorm_fwd with x_out = x + (float(delta_bf16) * ls[D]) - an fp32 product, then an fp32 sum: two roundings in that order,
+ *   never one fused multiply-add - and the LayerNorm of x_out as there (delta_bf16, ls and x_out are required).
+ * backward: lp_layernorm_bwd_bf16_colsum for a stream gradient that is consumed through a LayerScale: with o the updated dx_acc,
+ *   dx_bf16 = bf16(ls o o) (round to nearest even), colsum_acc[D] += sum_rows ls o o (of the fp32 products; NULL: not taken),
+ *   dls_acc[D] += sum_rows o o float(branch_bf16) - `ls` and `branch_bf16` (M, D) are the scale and the unscaled forward output (the `delta`
+ *   the forward read) of the branch that CONSUMES the emitted gradient.  dx_acc / dgamma_acc / dbeta_acc exactly as lp_layernorm_bwd; rows
+ *   without a dy (drop_T) still carry stream gradient and contribute to all three sums. */
+int lp_layernorm_ls_fwd(const float* x, const void* delta_bf16, const float* ls, float* x_out, const float* gamma, const float* beta, float eps,
+                        int M, int D, int drop_T, void* y_bf16, float* mean, float* rstd, lp_stream_t stream);
+int lp_layernorm_ls_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
+                        const void* branch_bf16, int M, int D, int drop_T, float* dx_acc, void* dx_bf16, float* dgamma_acc, float* dbeta_acc,
+                        float* colsum_acc, float* dls_acc, lp_stream_t stream);
 /* in place: s[r][:n] = softmax(scale * s[r][:n]), s[r][n:ld] = 0   /   dp <- scale * p * (dp - sum(dp * p)) */
 int lp_softmax_rows_fwd(void* s_bf16, int rows, int n, int ld, float scale, lp_stream_t stream);
 int lp_softmax_rows_bwd(const void* p_bf16, void* dp_bf16, int rows, int n, int ld, float scale, lp_stream_t stream);

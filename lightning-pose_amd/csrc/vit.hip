@@ -120,14 +120,29 @@ __device__ __forceinline__ float half_wave_sum(float v) {   // over the 32 lanes
     return v;
 }
 
-template <int NP>
-__global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const unsigned short* __restrict__ delta,
-                                                            float* __restrict__ x_out, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, float eps, int M, int D, int drop_T,
-                                                            unsigned short* __restrict__ y, float* __restrict__ mean,
-                                                            float* __restrict__ rstd) {
+// a * b, then + c: two roundings in that order, never one fused multiply-add (device code is compiled with -ffp-contract=fast-honor-pragmas)
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+    const float t = a * b;
+    return t + c;
+}
+
+// LS (DINOv2's LayerScale, lp_layernorm_ls_fwd): the branch output is scaled per channel in front of the residual add,
+// x_out = x + (delta * ls) - the D scales stay in registers across the rows of a lane, as gamma does in the backward walk
+template <int NP, bool LS>
+__device__ __forceinline__ void layernorm_fwd_rows(const float* __restrict__ x, const unsigned short* __restrict__ delta,
+                                                   const float* __restrict__ ls, float* __restrict__ x_out, const float* __restrict__ gamma,
+                                                   const float* __restrict__ beta, float eps, int M, int D, int drop_T,
+                                                   unsigned short* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, hl = lane & 31;
     const int pieces = D >> 2;
+    float lsv[LS ? NP : 1][4];
+    if (LS) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) lsv[LS ? p : 0][e] = hl + 32 * p < pieces ? ls[(hl + 32 * p) * 4 + e] : 0.f;
+    }
     for (int row0 = (blockIdx.x * 4 + wave) * 2; row0 < M; row0 += gridDim.x * 8) {
         const int row = row0 + half;
         const bool live = row < M;
@@ -146,7 +161,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
                     float d[4];
                     unpack4(*reinterpret_cast<const u16x4*>(delta + (size_t)row * D + pc * 4), d);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[p][e] += d[e];
+                    for (int e = 0; e < 4; ++e) v[p][e] = LS ? mul_then_add(d[e], lsv[LS ? p : 0][e], v[p][e]) : v[p][e] + d[e];
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) s += v[p][e];
@@ -196,20 +211,43 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     }
 }
 
+template <int NP>
+__global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const unsigned short* __restrict__ delta,
+                                                            float* __restrict__ x_out, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float eps, int M, int D, int drop_T,
+                                                            unsigned short* __restrict__ y, float* __restrict__ mean,
+                                                            float* __restrict__ rstd) {
+    layernorm_fwd_rows<NP, false>(x, delta, nullptr, x_out, gamma, beta, eps, M, D, drop_T, y, mean, rstd);
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void layernorm_ls_fwd_kernel(const float* __restrict__ x, const unsigned short* __restrict__ delta,
+                                                               const float* __restrict__ ls, float* __restrict__ x_out,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int M,
+                                                               int D, int drop_T, unsigned short* __restrict__ y, float* __restrict__ mean,
+                                                               float* __restrict__ rstd) {
+    layernorm_fwd_rows<NP, true>(x, delta, ls, x_out, gamma, beta, eps, M, D, drop_T, y, mean, rstd);
+}
+
 // dx += rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma;  per-workgroup partial d gamma / d beta -> atomics
 // COLSUM (round 3): also the column sums of the bf16 stream gradient it writes - that tensor is the dy of the NEXT Linear backward, and its
 // column sums are that layer's bias gradient: taken here, the weight gradient needs no bias pass and may run on the pipelined kernel.
 // Half a wave per row, as the forward kernel; NP = passes of 32 lanes x 4 columns that cover D (3 for ViT-S, 6 for ViT-B).
-template <bool COLSUM, int NP>
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short* __restrict__ dy, const float* __restrict__ x,
-                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                            const float* __restrict__ gamma, int M, int D, int drop_T,
-                                                            float* __restrict__ dx, unsigned short* __restrict__ dx_bf16,
-                                                            float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ colsum) {
-    __shared__ float red[COLSUM ? 3 : 2][8][128];  // [gamma|beta|column sum][wave, half][column of the current pass]
+// LS (DINOv2's LayerScale, lp_layernorm_ls_bwd): the bf16 gradient that leaves is consumed through a per-channel scale `ls`, so it is ls o o
+// (o: the updated stream gradient) - as are the column sums - and the scale's own gradient sum_rows o o branch is a fourth per-lane
+// accumulator next to d gamma / d beta / the column sums (`branch`: the unscaled forward output of that branch, read here once)
+template <bool COLSUM, bool LS, int NP>
+__device__ __forceinline__ void layernorm_bwd_rows(const unsigned short* __restrict__ dy, const float* __restrict__ x,
+                                                   const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                   const float* __restrict__ gamma, const float* __restrict__ ls,
+                                                   const unsigned short* __restrict__ branch, int M, int D, int drop_T, float* __restrict__ dx,
+                                                   unsigned short* __restrict__ dx_bf16, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                   float* __restrict__ colsum, float* __restrict__ dls) {
+    constexpr int kCs = 2, kLs = COLSUM ? 3 : 2;   // rows of `red` behind d gamma, d beta
+    __shared__ float red[2 + (COLSUM ? 1 : 0) + (LS ? 1 : 0)][8][128];  // [gamma|beta|column sum|scale][wave, half][column of the current pass]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, hl = lane & 31;
     const int pieces = D >> 2;
-    float ag[NP][4], ab[NP][4], gm[NP][4], ac[COLSUM ? NP : 1][4];
+    float ag[NP][4], ab[NP][4], gm[NP][4], ac[COLSUM ? NP : 1][4], al[LS ? NP : 1][4], lsv[LS ? NP : 1][4];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
         const int pc = hl + 32 * p;
@@ -218,6 +256,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
             ag[p][e] = ab[p][e] = 0.f;
             ac[COLSUM ? p : 0][e] = 0.f;
             gm[p][e] = pc < pieces ? gamma[pc * 4 + e] : 0.f;
+            if (LS) {
+                al[LS ? p : 0][e] = 0.f;
+                lsv[LS ? p : 0][e] = pc < pieces ? ls[pc * 4 + e] : 0.f;
+            }
         }
     }
     for (int row0 = (blockIdx.x * 4 + wave) * 2; row0 < M; row0 += gridDim.x * 8) {
@@ -265,6 +307,15 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] += rs * (g[p][e] - s1 - xh[p][e] * s2);
                 *dst = o;
+                if (LS) {   // what the branch behind the scale receives; the scale's gradient takes the unscaled o
+                    float br[4];
+                    unpack4(*reinterpret_cast<const u16x4*>(branch + (size_t)row * D + pc * 4), br);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        al[LS ? p : 0][e] = fmaf(o[e], br[e], al[LS ? p : 0][e]);
+                        o[e] *= lsv[LS ? p : 0][e];
+                    }
+                }
                 if (dx_bf16 != nullptr) {  // the updated residual-stream gradient as the next GEMM's operand (saves a cast pass)
                     typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
                     const u32x2_t w = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
@@ -286,7 +337,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
         for (int e = 0; e < 4; ++e) {
             red[0][wave * 2 + half][hl * 4 + e] = ag[p][e];
             red[1][wave * 2 + half][hl * 4 + e] = ab[p][e];
-            if (COLSUM) red[COLSUM ? 2 : 0][wave * 2 + half][hl * 4 + e] = ac[COLSUM ? p : 0][e];
+            if (COLSUM) red[COLSUM ? kCs : 0][wave * 2 + half][hl * 4 + e] = ac[COLSUM ? p : 0][e];
+            if (LS) red[LS ? kLs : 0][wave * 2 + half][hl * 4 + e] = al[LS ? p : 0][e];
         }
         __syncthreads();
         const int cl = threadIdx.x;            // column within this pass
@@ -297,9 +349,30 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
             };
             atomicAdd(&dgamma[c], total(0));
             atomicAdd(&dbeta[c], total(1));
-            if (COLSUM) atomicAdd(&colsum[c], total(COLSUM ? 2 : 0));
+            if (COLSUM) atomicAdd(&colsum[c], total(COLSUM ? kCs : 0));
+            if (LS) atomicAdd(&dls[c], total(LS ? kLs : 0));
         }
     }
+}
+
+template <bool COLSUM, int NP>
+__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short* __restrict__ dy, const float* __restrict__ x,
+                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                            const float* __restrict__ gamma, int M, int D, int drop_T,
+                                                            float* __restrict__ dx, unsigned short* __restrict__ dx_bf16,
+                                                            float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ colsum) {
+    layernorm_bwd_rows<COLSUM, false, NP>(dy, x, mean, rstd, gamma, nullptr, nullptr, M, D, drop_T, dx, dx_bf16, dgamma, dbeta, colsum, nullptr);
+}
+
+template <bool COLSUM, int NP>
+__global__ __launch_bounds__(256) void layernorm_ls_bwd_kernel(const unsigned short* __restrict__ dy, const float* __restrict__ x,
+                                                               const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                               const float* __restrict__ gamma, const float* __restrict__ ls,
+                                                               const unsigned short* __restrict__ branch, int M, int D, int drop_T,
+                                                               float* __restrict__ dx, unsigned short* __restrict__ dx_bf16,
+                                                               float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ colsum,
+                                                               float* __restrict__ dls) {
+    layernorm_bwd_rows<COLSUM, true, NP>(dy, x, mean, rstd, gamma, ls, branch, M, D, drop_T, dx, dx_bf16, dgamma, dbeta, colsum, dls);
 }
 
 // ---- GELU (exact, erf) on bf16 streams --------------------------------------------------------------------------------
@@ -667,6 +740,61 @@ extern "C" int lp_layernorm_bwd_bf16_colsum(const void* dy_bf16, const float* x,
                                             float* colsum_acc, lp_stream_t stream) {
     LP_REQUIRE(dx_bf16 && colsum_acc);
     return layernorm_bwd_impl(dy_bf16, x, mean, rstd, gamma, M, D, drop_T, dx_acc, dx_bf16, dgamma_acc, dbeta_acc, stream, colsum_acc);
+}
+
+// ---- LayerScale inside the two walks (DINOv2): include/lp_hip.h ----------------------------------------------------------------------
+extern "C" int lp_layernorm_ls_fwd(const float* x, const void* delta_bf16, const float* ls, float* x_out, const float* gamma, const float* beta,
+                                   float eps, int M, int D, int drop_T, void* y_bf16, float* mean, float* rstd, lp_stream_t stream) {
+    using namespace lp;
+    LP_REQUIRE(x && delta_bf16 && ls && x_out && gamma && beta && y_bf16 && mean && rstd && M > 0 && D > 0 && drop_T >= 0);
+    if (D > kLnMaxD || D % 4 != 0) return LP_ERR_UNSUPPORTED;
+    int blocks = (M + 7) / 8;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+#define LP_LN_FWD(NP_)                                                                                                                         \
+    hipLaunchKernelGGL((layernorm_ls_fwd_kernel<NP_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (const unsigned short*)delta_bf16, \
+                       ls, x_out, gamma, beta, eps, M, D, drop_T, (unsigned short*)y_bf16, mean, rstd)
+    switch ((D + 127) / 128) {
+    case 1: LP_LN_FWD(1); break;
+    case 2: LP_LN_FWD(2); break;
+    case 3: LP_LN_FWD(3); break;
+    case 4: LP_LN_FWD(4); break;
+    case 5: case 6: LP_LN_FWD(6); break;
+    default: LP_LN_FWD(8); break;
+    }
+#undef LP_LN_FWD
+    return launch_status();
+}
+
+extern "C" int lp_layernorm_ls_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
+                                   const void* branch_bf16, int M, int D, int drop_T, float* dx_acc, void* dx_bf16, float* dgamma_acc,
+                                   float* dbeta_acc, float* colsum_acc, float* dls_acc, lp_stream_t stream) {
+    using namespace lp;
+    LP_REQUIRE(dy_bf16 && x && mean && rstd && gamma && ls && branch_bf16 && dx_acc && dx_bf16 && dgamma_acc && dbeta_acc && dls_acc && M > 0 &&
+               D > 0 && drop_T >= 0);
+    if (D > kLnMaxD || D % 4 != 0) return LP_ERR_UNSUPPORTED;
+    int blocks = (M + 7) / 8;
+    if (blocks > 2048) blocks = 2048;  // (as layernorm_bwd_impl)
+#define LP_LN_BWD(CS_, NP_)                                                                                                                      \
+    hipLaunchKernelGGL((layernorm_ls_bwd_kernel<CS_, NP_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)dy_bf16, x,  \
+                       mean, rstd, gamma, ls, (const unsigned short*)branch_bf16, M, D, drop_T, dx_acc, (unsigned short*)dx_bf16, dgamma_acc,     \
+                       dbeta_acc, colsum_acc, dls_acc)
+#define LP_LN_BWD_NP(CS_)                        \
+    switch ((D + 127) / 128) {                   \
+    case 1: LP_LN_BWD(CS_, 1); break;            \
+    case 2: LP_LN_BWD(CS_, 2); break;            \
+    case 3: LP_LN_BWD(CS_, 3); break;            \
+    case 4: LP_LN_BWD(CS_, 4); break;            \
+    case 5: case 6: LP_LN_BWD(CS_, 6); break;    \
+    default: LP_LN_BWD(CS_, 8); break;           \
+    }
+    if (colsum_acc != nullptr) {
+        LP_LN_BWD_NP(true)
+    } else {
+        LP_LN_BWD_NP(false)
+    }
+#undef LP_LN_BWD_NP
+#undef LP_LN_BWD
+    return launch_status();
 }
 
 extern "C" int lp_gelu_fwd(const void* x_bf16, size_t n, void* y_bf16, lp_stream_t stream) {

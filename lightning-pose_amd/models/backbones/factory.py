@@ -8,13 +8,18 @@ from __future__ import annotations
 RESNET50_VARIANTS = ("resnet50", "resnet50_animal_apose", "resnet50_animal_ap10k", "resnet50_human_jhmdb", "resnet50_human_res_rle",
                      "resnet50_human_top_res", "resnet50_human_hand")
 
-BACKBONE_STRIDES: dict[str, int] = {**{n: 32 for n in RESNET50_VARIANTS}, "vits_dino": 16, "vitb_dino": 16}
+BACKBONE_STRIDES: dict[str, int] = {**{n: 32 for n in RESNET50_VARIANTS}, "vits_dino": 16, "vitb_dino": 16, "vits_dinov2": 16, "vitb_dinov2": 16}
 
 # name -> number of output features
-_IMPLEMENTED = {**{n: 2048 for n in RESNET50_VARIANTS}, "vits_dino": 384, "vitb_dino": 768}
+_IMPLEMENTED = {**{n: 2048 for n in RESNET50_VARIANTS}, "vits_dino": 384, "vitb_dino": 768, "vits_dinov2": 384, "vitb_dinov2": 768}
 
 # ViT variants: (hidden, depth, heads, mlp, patch, pretraining grid) of facebook/dino-vit{s,b}16
 VIT_CONFIGS = {"vits_dino": (384, 12, 6, 1536, 16, 14), "vitb_dino": (768, 12, 12, 3072, 16, 14)}
+
+# DINOv2 variants, same fields: facebook/dinov2-{small,base} with the patch projection resampled from 14 to 16 px (reference
+# models/backbones/vit_dino.py; the 37 x 37 position table is that of the 518-px pretraining).  A table of their own: VIT_CONFIGS is also the
+# list of backbones the multi-view transformer tracker accepts, and DINOv2 is single-view only.
+DINOV2_CONFIGS = {"vits_dinov2": (384, 12, 6, 1536, 16, 37), "vitb_dinov2": (768, 12, 12, 3072, 16, 37)}
 
 
 def backbone_features(backbone_arch: str) -> int:

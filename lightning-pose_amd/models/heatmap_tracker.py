@@ -21,7 +21,8 @@ from ..engine import Engine
 from ..losses.losses import RegressionRMSELoss
 from .backbones import backbone_features
 from .backbones._init import head_state_dict, seeded_state_dict, vit_seeded_state_dict
-from .backbones.factory import VIT_CONFIGS
+from .backbones.dinov2 import dinov2_seeded_state_dict, load_dinov2_checkpoint
+from .backbones.factory import DINOV2_CONFIGS, VIT_CONFIGS
 from .base import BaseSupervisedTracker, SemiSupervisedTrackerMixin
 from .datatypes import HeatmapTrackerLabeledOutputsDict, HeatmapTrackerUnlabeledOutputsDict
 from .heads.heatmap import HeatmapHead, _Holder
@@ -76,19 +77,27 @@ class HeatmapTracker(BaseSupervisedTracker):
                                 downsample_factor=downsample_factor, _bound=True)
         self.backbone = _Holder()
         checkpoint = kwargs.get("backbone_checkpoint")
-        if backbone in VIT_CONFIGS:
+        if backbone in VIT_CONFIGS or backbone in DINOV2_CONFIGS:
             from ..vit_engine import ViTEngine
-            hidden, depth, heads, mlp, patch, grid = VIT_CONFIGS[backbone]
+            dinov2 = backbone not in VIT_CONFIGS
+            hidden, depth, heads, mlp, patch, grid = (DINOV2_CONFIGS if dinov2 else VIT_CONFIGS)[backbone]
             engine_cls = ViTEngine
             if self.precision == "fp32":  # validation mode (vit_engine_fp32.py)
                 from ..vit_engine_fp32 import Fp32ViTEngine as engine_cls
             engine_kwargs, extra_init = self._vit_engine_extras(hidden)
+            if dinov2:   # (transformers Dinov2Model: LayerScale, LayerNorm eps 1e-6, its own parameter names - vit_engine.py)
+                engine_kwargs["arch"] = "dinov2"
             self.net = engine_cls(num_keypoints, downsample_factor, device, hidden=hidden, depth=depth, heads=heads, mlp=mlp, patch=patch,
                                  pretrain_grid=grid, **engine_kwargs)
-            init = vit_seeded_state_dict(hidden, depth, heads, mlp, patch, grid)
+            init = (dinov2_seeded_state_dict if dinov2 else vit_seeded_state_dict)(hidden, depth, heads, mlp, patch, grid)
             init.update(head_state_dict(self.num_fc_input_features, num_keypoints, self.head.n_layers))
             init.update(extra_init)
-            if pretrained:
+            if pretrained and dinov2:
+                if checkpoint is None:
+                    raise RuntimeError("pretrained=True needs the DINOv2 weights, which cannot be downloaded here; pass backbone_checkpoint="
+                                       "<state_dict / safetensors file of facebook/dinov2-small or dinov2-base> or pretrained=False")
+                load_dinov2_checkpoint(str(checkpoint), init, patch)   # (a 14 x 14 patch projection is resampled to 16 x 16)
+            elif pretrained:
                 if checkpoint is None:
                     raise RuntimeError("pretrained=True needs the DINO weights, which cannot be downloaded here; pass "
                                        "backbone_checkpoint=<state_dict / safetensors file of facebook/dino-vits16> or pretrained=False")

@@ -32,6 +32,7 @@ from .engine import ConvP, Engine, Tape, build_head
 from .ops import _p
 
 LN_EPS = 1e-12  # ViTConfig.layer_norm_eps
+DINOV2_LN_EPS = 1e-6  # Dinov2Config.layer_norm_eps
 
 
 def bicubic_matrix(n_in: int, n_out: int) -> np.ndarray:
@@ -74,8 +75,9 @@ class LNP:
 
 class ViTPlan:
     def __init__(self, num_keypoints: int, downsample_factor: int, D: int, depth: int, heads: int, mlp: int, patch: int, n_pos: int,
-                 num_views: int = 0):
+                 num_views: int = 0, arch: str = "vit"):
         self.D, self.depth, self.heads, self.mlp, self.patch, self.n_pos = D, depth, heads, mlp, patch, n_pos
+        self.arch = arch
         pre = "backbone.vision_encoder"
         off = wd = 0
         # multi-view mode: the (V, D) view embeddings lead the flat buffers.  Their gradient is, with the other embeddings', the LAST to
@@ -98,13 +100,26 @@ class ViTPlan:
             off += 2 * D
             return l
 
-        self.cls_off = off
-        off += D
+        def vec():
+            nonlocal off
+            off += D
+            return off - D
+
+        self.cls_off = vec()
+        # DINOv2 (transformers Dinov2Model): embeddings.mask_token (1, D), which the forward pass never reads, and per layer the two
+        # LayerScale vectors - all inside the backbone's range, each layer's own parameters still one contiguous run (grad_progress)
+        self.mask_off = vec() if arch == "dinov2" else None
         self.pos_off = off
         off += n_pos * D
         self.patch_lin = lin(f"{pre}.embeddings.patch_embeddings.projection", D, 3 * patch * patch)
         self.layers = []
         for i in range(depth):
+            if arch == "dinov2":
+                p = f"{pre}.encoder.layer.{i}"
+                self.layers.append(dict(
+                    ln1=ln(f"{p}.norm1"), qkv=lin(f"{p}.attention.attention.qkv", 3 * D, D), proj=lin(f"{p}.attention.output.dense", D, D),
+                    ls1=vec(), ln2=ln(f"{p}.norm2"), fc1=lin(f"{p}.mlp.fc1", mlp, D), fc2=lin(f"{p}.mlp.fc2", D, mlp), ls2=vec()))
+                continue
             p = f"{pre}.layers.{i}"
             self.layers.append(dict(
                 ln1=ln(f"{p}.layernorm_before"), qkv=lin(f"{p}.attention.qkv", 3 * D, D), proj=lin(f"{p}.attention.o_proj", D, D),
@@ -151,14 +166,22 @@ class ViTEngine(Engine):
     ``num_views`` = V > 0 selects the multi-view mode (reference models/heatmap_tracker_multiview.py:143-223, ``forward_vit``): the batch is
     B * V images, row b * V + v view v of sample b; the tokens carry no [CLS] row but a learned ``view_embeddings[v]`` (V, D), and the layers
     attend over the V * Np tokens of a sample at once (``lp_vit_mv_tokens_fwd`` / ``_bwd``; everything after the token assembly is the same
-    kernels with B sequences of V * Np tokens).  ``cls_token`` and row 0 of the position table stay in the state dict with a zero gradient."""
+    kernels with B sequences of V * Np tokens).  ``cls_token`` and row 0 of the position table stay in the state dict with a zero gradient.
+
+    ``arch="dinov2"`` is transformers' ``Dinov2Model`` (the reference's ``VisionEncoderDino``, models/backbones/vit_dino.py, behind
+    "vits_dinov2" / "vitb_dinov2"; its 14-px patch projection arrives resampled to 16 px, models/backbones/dinov2.py): the same layers with
+    a LayerScale on each branch output, LayerNorm eps 1e-6, a ``mask_token`` parameter the forward pass never reads, and that model's
+    parameter names.  LayerScale costs no launch: ``lp_layernorm_ls_fwd`` scales the branch output inside the residual add,
+    ``lp_layernorm_ls_bwd`` emits the scaled gradient, its column sums and the scale's own gradient; the tape keeps the two
+    unscaled branch outputs of every layer for the latter.  Single-view only."""
 
     wgrad_side_stream = False
     _patch_dtype = torch.bfloat16
     _token_kernels = ("lp_vit_tokens_fwd", "lp_vit_tokens_bwd", "lp_vit_mv_tokens_fwd", "lp_vit_mv_tokens_bwd")
 
     def __init__(self, num_keypoints: int, downsample_factor: int = 2, device: torch.device | str = "cuda:0", hidden: int = 384,
-                 depth: int = 12, heads: int = 6, mlp: int = 1536, patch: int = 16, pretrain_grid: int = 14, num_views: int = 0):
+                 depth: int = 12, heads: int = 6, mlp: int = 1536, patch: int = 16, pretrain_grid: int = 14, num_views: int = 0,
+                 arch: str = "vit"):
         self.device = torch.device(device)
         ops.require_device_type(self.device)
         self._lib = _lib.lib()
@@ -168,7 +191,14 @@ class ViTEngine(Engine):
         self.grid0 = pretrain_grid
         if num_views < 0:
             raise ValueError(f"num_views must be positive (0: single-view tokens with [CLS]), got {num_views}")
-        self.plan = ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, 1 + pretrain_grid * pretrain_grid, num_views)
+        if arch not in ("vit", "dinov2"):
+            raise ValueError(f'arch must be "vit" or "dinov2", got {arch!r}')
+        if arch == "dinov2" and num_views:
+            raise NotImplementedError("the multi-view token assembly (num_views > 0) is not implemented for the DINOv2 backbones")
+        self.arch = arch
+        self.ln_eps = DINOV2_LN_EPS if arch == "dinov2" else LN_EPS
+        self.plan = ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, 1 + pretrain_grid * pretrain_grid, num_views,
+                            arch)
         n, dev = self.plan.n_total, self.device
         self.P = torch.zeros(n, device=dev, dtype=torch.float32)
         self.G = torch.zeros(n, device=dev, dtype=torch.float32)
@@ -177,6 +207,10 @@ class ViTEngine(Engine):
         self.R = torch.zeros(0, device=dev, dtype=torch.float32)
         for l in self.plan.norms():
             self.P[l.g_off:l.g_off + hidden] = 1.0
+        for L in self.plan.layers:   # (Dinov2Config.layerscale_value = 1.0)
+            for o in (L.get("ls1"), L.get("ls2")):
+                if o is not None:
+                    self.P[o:o + hidden] = 1.0
         self.nbt = torch.zeros((), dtype=torch.long)
         self.sync_bn, self.process_group = False, None   # no BatchNorm here; kept for the DataParallel wrapper
         self.sync_bn_messages = 0
@@ -194,12 +228,14 @@ class ViTEngine(Engine):
         pre = "backbone.vision_encoder"
         sd = {"view_embeddings": buf[pl.view_off:pl.n_view].view(pl.num_views, D)} if pl.num_views else {}
         sd[f"{pre}.embeddings.cls_token"] = buf[pl.cls_off:pl.cls_off + D].view(1, 1, D)
+        if pl.mask_off is not None:
+            sd[f"{pre}.embeddings.mask_token"] = buf[pl.mask_off:pl.mask_off + D].view(1, D)
         sd[f"{pre}.embeddings.position_embeddings"] = buf[pl.pos_off:pl.pos_off + pl.n_pos * D].view(1, pl.n_pos, D)
         for l in pl.linears():
             w, b = buf[l.w_off:l.w_off + l.N * l.K], buf[l.b_off:l.b_off + l.N]
             if l.name.endswith("attention.qkv"):  # fused [q; k; v]: three reference parameters share one GEMM weight
                 stem = l.name[:-len("qkv")]
-                for j, nm in enumerate(("q_proj", "k_proj", "v_proj")):
+                for j, nm in enumerate(("query", "key", "value") if pl.arch == "dinov2" else ("q_proj", "k_proj", "v_proj")):
                     sd[f"{stem}{nm}.weight"] = w[j * D * D:(j + 1) * D * D].view(D, D)
                     sd[f"{stem}{nm}.bias"] = b[j * D:(j + 1) * D]
             elif l is pl.patch_lin:
@@ -211,6 +247,10 @@ class ViTEngine(Engine):
         for l in pl.norms():
             sd[f"{l.name}.weight"] = buf[l.g_off:l.g_off + D]
             sd[f"{l.name}.bias"] = buf[l.b_off:l.b_off + D]
+        if pl.arch == "dinov2":
+            for i, L in enumerate(pl.layers):
+                for nm in ("1", "2"):
+                    sd[f"{pre}.encoder.layer.{i}.layer_scale{nm}.lambda1"] = buf[L["ls" + nm]:L["ls" + nm] + D]
         for c in pl.head:
             sd[f"{c.name}.weight"] = self.param_view(c, "weight", buf=buf)
             sd[f"{c.name}.bias"] = self.param_view(c, "bias", buf=buf)
@@ -236,7 +276,8 @@ class ViTEngine(Engine):
 
     @torch.no_grad()
     def load_state_dict(self, sd: dict[str, torch.Tensor], strict: bool = True) -> None:
-        sd = {self.canonical_key(k): v for k, v in sd.items()}
+        if self.arch != "dinov2":   # (Dinov2Model's own names are the 4.x-style ones: nothing to translate)
+            sd = {self.canonical_key(k): v for k, v in sd.items()}
         own = self.state_dict()
         missing = [k for k in own if k not in sd]
         unexpected = [k for k in sd if k not in own]
@@ -327,20 +368,34 @@ class ViTEngine(Engine):
                     nbytes=2.0 * (M * l.K + M * l.N + l.N * l.K))
         return dx
 
-    def _ln(self, x, delta, l: LNP, M: int, drop_T: int = 0):
+    def _ln(self, x, delta, l: LNP, M: int, drop_T: int = 0, ls: int | None = None):
+        """``ls``: offset of the LayerScale vector that scales ``delta`` in front of the residual add (DINOv2)"""
         D = self.plan.D
         xo = torch.empty_like(x) if delta is not None else None
         rows = M - M // drop_T if drop_T else M
         y = torch.empty(rows, D, device=self.device, dtype=torch.bfloat16)
         mean = torch.empty(M, device=self.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
-        check(self._lib.lp_layernorm_fwd(_p(x), _p(delta), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]), LN_EPS, M, D, drop_T, _p(y),
+        if ls is not None and delta is not None:
+            check(self._lib.lp_layernorm_ls_fwd(_p(x), _p(delta), _p(self.P[ls:]), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]), self.ln_eps,
+                                                M, D, drop_T, _p(y), _p(mean), _p(rstd), ops._stream()), "lp_layernorm_ls_fwd")
+            return y, mean, rstd, xo
+        check(self._lib.lp_layernorm_fwd(_p(x), _p(delta), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]), self.ln_eps, M, D, drop_T, _p(y),
                                          _p(mean), _p(rstd), ops._stream()), "lp_layernorm_fwd")
         return y, mean, rstd, (xo if xo is not None else x)
 
-    def _ln_bwd(self, dy, x, mean, rstd, l: LNP, M: int, dx, drop_T: int = 0, want_bf16: bool = False, colsum: torch.Tensor | None = None):
+    def _ln_bwd(self, dy, x, mean, rstd, l: LNP, M: int, dx, drop_T: int = 0, want_bf16: bool = False, colsum: torch.Tensor | None = None,
+                ls: int | None = None, branch: torch.Tensor | None = None):
         """dx (fp32, the residual stream's gradient) += LayerNorm backward of dy; ``want_bf16``: also return the updated dx in bf16;
-        ``colsum``: accumulate that bf16 tensor's column sums there (the bias gradient of the Linear layer it is the dy of)"""
+        ``colsum``: accumulate that bf16 tensor's column sums there (the bias gradient of the Linear layer it is the dy of);
+        ``ls`` / ``branch`` (DINOv2): the returned tensor feeds a branch through the LayerScale vector at offset ``ls`` - it leaves scaled, and
+        the scale's gradient (against ``branch``, that branch's unscaled forward output) is accumulated into G"""
+        if want_bf16 and ls is not None:
+            out = torch.empty(M, self.plan.D, device=self.device, dtype=torch.bfloat16)
+            check(self._lib.lp_layernorm_ls_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _p(self.P[l.g_off:]), _p(self.P[ls:]), _p(branch), M, self.plan.D,
+                                                drop_T, _p(dx), _p(out), _p(self.G[l.g_off:]), _p(self.G[l.b_off:]), _p(colsum), _p(self.G[ls:]),
+                                                ops._stream()), "lp_layernorm_ls_bwd")
+            return out
         if want_bf16 and colsum is not None:
             out = torch.empty(M, self.plan.D, device=self.device, dtype=torch.bfloat16)
             check(self._lib.lp_layernorm_bwd_bf16_colsum(_p(dy), _p(x), _p(mean), _p(rstd), _p(self.P[l.g_off:]), M, self.plan.D, drop_T, _p(dx),
@@ -474,7 +529,7 @@ class ViTEngine(Engine):
         scale = 1.0 / math.sqrt(D // nh)
         qs = 3 * D  # row pitch of the fused qkv tensor
         for i, L in enumerate(pl.layers):
-            y1, m1, r1, x = self._ln(x, delta, L["ln1"], M)
+            y1, m1, r1, x = self._ln(x, delta, L["ln1"], M, ls=pl.layers[i - 1].get("ls2") if i else None)
             qkv = self._linear(y1, L["qkv"], M)
             # P = softmax(Q K^T / 8) (bf16, row pitch Tp, pad columns zero; kept for the backward pass) and attn = P V in one kernel:
             # the scores themselves never reach memory
@@ -486,14 +541,16 @@ class ViTEngine(Engine):
                 nbytes=2.0 * (3 * Bs * Tn * D + Bs * Tn * D) + (2.0 * Bs * nh * Tn * Tp if S is not None else 0.0))
             proj = self._linear(attn, L["proj"], M)
             x_in = x
-            y2, m2, r2, x = self._ln(x, proj, L["ln2"], M)
+            y2, m2, r2, x = self._ln(x, proj, L["ln2"], M, ls=L.get("ls1"))
             h1, a1 = self._linear_gelu(y2, L["fc1"], M)
             delta = self._linear(a1, L["fc2"], M)
             if keep:
                 for nm, v in (("x_in", x_in), ("m1", m1), ("r1", r1), ("y1", y1), ("qkv", qkv), ("P", S), ("attn", attn), ("x_mid", x),
                               ("m2", m2), ("r2", r2), ("y2", y2), ("h1", h1), ("a1", a1)):
                     T[f"l{i}.{nm}"] = v
-        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T)
+                if "ls1" in L:   # the unscaled branch outputs: the LayerScale gradients are taken against them
+                    T[f"l{i}.proj"], T[f"l{i}.fc2"] = proj, delta
+        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"))
         if keep:
             T["x_last"], T["mf"], T["rf"] = x, mf, rf
         heat = self._head_forward(feat.view(B, gh, gw, D), B, gh, gw, T if keep else {})
@@ -523,7 +580,15 @@ class ViTEngine(Engine):
         fuse_bias = os.environ.get("LP_VIT_BIAS_FUSED", "1") != "0"
         fuse_gelu = os.environ.get("LP_VIT_GELU_FUSED", "1") != "0"   # (0: A/B runs - lp_gemm_nt, then lp_gelu_bwd_colsum)
         bsum = (lambda lin: self.G[lin.b_off:lin.b_off + lin.N]) if fuse_bias else (lambda lin: None)
-        dx16 = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, colsum=bsum(pl.layers[-1]["fc2"]))
+        # (DINOv2: each of them also applies the LayerScale of the branch its bf16 output feeds, and leaves that scale's gradient)
+        def scaled(j: int, nm: str) -> dict:
+            """_ln_bwd's LayerScale arguments for the gradient that feeds branch ``nm`` ("1": attention, "2": MLP) of layer j; {} for the ViT"""
+            if "ls1" not in pl.layers[j]:
+                return {}
+            return dict(ls=pl.layers[j]["ls" + nm], branch=T[f"l{j}." + ("proj" if nm == "1" else "fc2")])
+
+        dx16 = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, colsum=bsum(pl.layers[-1]["fc2"]),
+                            **scaled(pl.depth - 1, "2"))
 
         for i in range(pl.depth - 1, -1, -1):
             L = pl.layers[i]
@@ -547,7 +612,7 @@ class ViTEngine(Engine):
             d_y2 = self._linear_bwd(L["fc1"], t("y2"), d_h1, M, bias_done=fuse_bias)
             # (proj keeps the bias sums inside its weight-gradient launch: a 384 x 384 layer gains 5 us from the pipelined kernel, the
             #  column sums cost the LayerNorm backward 40 - profiles/archive/r03_final_vit_kernel_stats.txt)
-            dx16 = self._ln_bwd(d_y2, t("x_mid"), t("m2"), t("r2"), L["ln2"], M, dx, want_bf16=True)
+            dx16 = self._ln_bwd(d_y2, t("x_mid"), t("m2"), t("r2"), L["ln2"], M, dx, want_bf16=True, **scaled(i, "1"))
             # ---- attention branch: x_mid = x_in + proj(softmax(Q K^T / 8) V)
             dproj = dx16
             d_attn = self._linear_bwd(L["proj"], t("attn"), dproj, M)
@@ -572,7 +637,7 @@ class ViTEngine(Engine):
                 trace[f"l{i}.dqkv"] = dqkv
             d_y1 = self._linear_bwd(L["qkv"], t("y1"), dqkv, M)
             dx16 = self._ln_bwd(d_y1, t("x_in"), t("m1"), t("r1"), L["ln1"], M, dx, want_bf16=i > 0,
-                                colsum=bsum(pl.layers[i - 1]["fc2"]) if i > 0 else None)
+                                colsum=bsum(pl.layers[i - 1]["fc2"]) if i > 0 else None, **(scaled(i - 1, "2") if i > 0 else {}))
             if progress is not None:
                 progress(L["ln1"].g_off)  # everything from this layer's first parameter to the end of G is final
         if trace is not None:

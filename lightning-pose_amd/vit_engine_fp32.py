@@ -17,7 +17,7 @@ from ._lib import check
 from .engine import Tape
 from .engine_fp32 import Fp32Engine
 from .ops import _p
-from .vit_engine import LN_EPS, Lin, LNP, ViTEngine
+from .vit_engine import Lin, LNP, ViTEngine
 
 
 class Fp32ViTEngine(ViTEngine):
@@ -58,17 +58,27 @@ class Fp32ViTEngine(ViTEngine):
               "lp_f32_conv_dgrad(linear)")
         return dx
 
-    def _ln(self, x, delta, l: LNP, M: int, drop_T: int = 0):
+    def _ln(self, x, delta, l: LNP, M: int, drop_T: int = 0, ls: int | None = None):
         D = self.plan.D
         xo = torch.empty_like(x) if delta is not None else None
         rows = M - M // drop_T if drop_T else M
         y = self._f32(rows, D)
         mean, rstd = self._f32(M), self._f32(M)
-        check(self._lib.lp_f32_layernorm_fwd(_p(x), _p(delta), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]), LN_EPS, M, D, drop_T, _p(y),
+        if ls is not None and delta is not None:   # DINOv2: x_out = x + (delta * LayerScale)
+            check(self._lib.lp_f32_layernorm_ls_fwd(_p(x), _p(delta), _p(self.P[ls:]), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]),
+                                                    self.ln_eps, M, D, drop_T, _p(y), _p(mean), _p(rstd), ops._stream()), "lp_f32_layernorm_ls_fwd")
+            return y, mean, rstd, xo
+        check(self._lib.lp_f32_layernorm_fwd(_p(x), _p(delta), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]), self.ln_eps, M, D, drop_T, _p(y),
                                              _p(mean), _p(rstd), ops._stream()), "lp_f32_layernorm_fwd")
         return y, mean, rstd, (xo if xo is not None else x)
 
-    def _ln_bwd(self, dy, x, mean, rstd, l: LNP, M: int, dx, drop_T: int = 0, want_bf16: bool = False):
+    def _ln_bwd(self, dy, x, mean, rstd, l: LNP, M: int, dx, drop_T: int = 0, want_bf16: bool = False, ls: int | None = None, branch=None):
+        if want_bf16 and ls is not None:   # DINOv2: the operand of the next Linear backward leaves through the LayerScale at offset ``ls``
+            out = self._f32(M, self.plan.D)
+            check(self._lib.lp_f32_layernorm_ls_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _p(self.P[l.g_off:]), _p(self.P[ls:]), _p(branch), M,
+                                                    self.plan.D, drop_T, _p(dx), _p(out), _p(self.G[l.g_off:]), _p(self.G[l.b_off:]), None,
+                                                    _p(self.G[ls:]), ops._stream()), "lp_f32_layernorm_ls_bwd")
+            return out
         check(self._lib.lp_f32_layernorm_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _p(self.P[l.g_off:]), M, self.plan.D, drop_T, _p(dx),
                                              _p(self.G[l.g_off:]), _p(self.G[l.b_off:]), ops._stream()), "lp_f32_layernorm_bwd")
         return dx.clone() if want_bf16 else None   # (the operand of the next Linear backward: dx itself moves on in place)
@@ -108,14 +118,14 @@ class Fp32ViTEngine(ViTEngine):
         scale = 1.0 / math.sqrt(D // nh)
         qs = 3 * D
         for i, L in enumerate(pl.layers):
-            y1, m1, r1, x = self._ln(x, delta, L["ln1"], M)
+            y1, m1, r1, x = self._ln(x, delta, L["ln1"], M, ls=pl.layers[i - 1].get("ls2") if i else None)
             qkv = self._linear(y1, L["qkv"], M)
             Pm = self._f32(Bs * nh * Tn, Tn)
             attn = self._f32(M, D)
             check(self._lib.lp_f32_attn_fwd(_p(qkv), qs, D, 2 * D, Bs, nh, Tn, scale, _p(Pm), _p(attn), D, ops._stream()), "lp_f32_attn_fwd")
             proj = self._linear(attn, L["proj"], M)
             x_in = x
-            y2, m2, r2, x = self._ln(x, proj, L["ln2"], M)
+            y2, m2, r2, x = self._ln(x, proj, L["ln2"], M, ls=L.get("ls1"))
             h1 = self._linear(y2, L["fc1"], M)
             a1 = torch.empty_like(h1)
             check(self._lib.lp_f32_gelu_fwd(_p(h1), h1.numel(), _p(a1), ops._stream()), "lp_f32_gelu_fwd")
@@ -124,7 +134,9 @@ class Fp32ViTEngine(ViTEngine):
                 for nm, v in (("x_in", x_in), ("m1", m1), ("r1", r1), ("y1", y1), ("qkv", qkv), ("P", Pm), ("attn", attn), ("x_mid", x),
                               ("m2", m2), ("r2", r2), ("y2", y2), ("h1", h1), ("a1", a1)):
                     T[f"l{i}.{nm}"] = v
-        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T)
+                if "ls1" in L:   # the unscaled branch outputs: the LayerScale gradients are taken against them
+                    T[f"l{i}.proj"], T[f"l{i}.fc2"] = proj, delta
+        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"))
         T["x_last"], T["mf"], T["rf"] = x, mf, rf
         heat = self._head_forward(feat.view(B, gh, gw, D), B, gh, gw, T)
         tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training, seq=(Bs, Tn, drop_T))
@@ -141,7 +153,13 @@ class Fp32ViTEngine(ViTEngine):
         qs = 3 * D
         d_feat = self._head_backward(T, B, g_heat).contiguous()            # (B, gh, gw, D) fp32
         dx = torch.zeros(M, D, device=self.device, dtype=torch.float32)   # gradient of the residual stream
-        dcur = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True)
+        def scaled(j: int, nm: str) -> dict:
+            """_ln_bwd's LayerScale arguments for the gradient that feeds branch ``nm`` ("1": attention, "2": MLP) of layer j; {} for the ViT"""
+            if "ls1" not in pl.layers[j]:
+                return {}
+            return dict(ls=pl.layers[j]["ls" + nm], branch=T[f"l{j}." + ("proj" if nm == "1" else "fc2")])
+
+        dcur = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, **scaled(pl.depth - 1, "2"))
         for i in range(pl.depth - 1, -1, -1):
             L = pl.layers[i]
             t = lambda nm: T[f"l{i}.{nm}"]  # noqa: E731
@@ -151,7 +169,7 @@ class Fp32ViTEngine(ViTEngine):
             d_h1 = torch.empty_like(d_a1)
             check(self._lib.lp_f32_gelu_bwd(_p(t("h1")), _p(d_a1), d_a1.numel(), _p(d_h1), ops._stream()), "lp_f32_gelu_bwd")
             d_y2 = self._linear_bwd(L["fc1"], t("y2"), d_h1, M)
-            dcur = self._ln_bwd(d_y2, t("x_mid"), t("m2"), t("r2"), L["ln2"], M, dx, want_bf16=True)
+            dcur = self._ln_bwd(d_y2, t("x_mid"), t("m2"), t("r2"), L["ln2"], M, dx, want_bf16=True, **scaled(i, "1"))
             d_attn = self._linear_bwd(L["proj"], t("attn"), dcur, M)
             dqkv = self._f32(M, qs)
             dS = self._f32(Bs * nh * Tn, Tn)
@@ -160,7 +178,7 @@ class Fp32ViTEngine(ViTEngine):
             if trace is not None:
                 trace[f"l{i}.dqkv"] = dqkv
             d_y1 = self._linear_bwd(L["qkv"], t("y1"), dqkv, M)
-            dcur = self._ln_bwd(d_y1, t("x_in"), t("m1"), t("r1"), L["ln1"], M, dx, want_bf16=i > 0)
+            dcur = self._ln_bwd(d_y1, t("x_in"), t("m1"), t("r1"), L["ln1"], M, dx, want_bf16=i > 0, **(scaled(i - 1, "2") if i > 0 else {}))
         if trace is not None:
             trace["tokens.dx"] = dx
         dpatch = self._tokens_bwd(dx, B, Np, gh, gw)

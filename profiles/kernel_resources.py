@@ -21,7 +21,9 @@ HOT = ("lp::conv_pipe_kernel", "lp::conv_spec_kernel", "lp::conv_wgrad_pipe_kern
        "lp::conv_igemm_kernel", "lp::bn_apply_kernel", "lp::bn_bwd_apply_kernel", "lp::bn_relu_maxpool_fwd_kernel", "lp::bn_pool_bwd_v2_kernel",
        "lp::colreduce_kernel", "lp::rows_reduce_kernel", "lp::decode_fwd_kernel", "lp::decode_bwd_kernel", "lp::heatmap_gen_kernel",
        "lp::hm_rowsq_kernel", "lp::hm_grad_kernel", "lp::softmax2d", "lp::adam_kernel", "lp::pca_kernel", "lp::temporal_kernel",
-       "lp::attn_fwd_kernel", "lp::attn_bwd_kv_kernel", "lp::pixel_shuffle")
+       "lp::attn_fwd_kernel", "lp::attn_bwd_kv_kernel", "lp::pixel_shuffle",
+       # the DINOv2 step's LayerNorm walks: four per-lane accumulator arrays at NP = 6 (ViT-B) must stay in registers
+       "lp::layernorm_ls_fwd_kernel", "lp::layernorm_ls_bwd_kernel")
 # decode_bwd_kernel<R, TY, NE = 64, ...> is the catch-all instantiation for maps larger than any BASELINE config selects (ne > 18 elements per
 # thread: heat-maps above 96 x 96 at 512 threads); it keeps its element array in scratch by design
 ALLOWED_SCRATCH = (
