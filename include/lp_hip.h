@@ -398,6 +398,8 @@ int lp_f32_vit_tokens_bwd(const float* dx, int B, int Np, int D, float* dpatch, 
 int lp_f32_vit_mv_tokens_fwd(const float* patch, const float* pos, const float* view, int B, int V, int Np, int D, float* x, lp_stream_t stream);
 int lp_f32_vit_mv_tokens_bwd(const float* dx, int B, int V, int Np, int D, float* dpatch, float* dpos, float* dview, void* workspace,
                              size_t workspace_bytes, lp_stream_t stream);
+/* as lp_layernorm_fwd (below) with delta, y in fp32 and any D, except: with delta == NULL x_out is ignored and left unwritten (the
+ * normalised tensor is x itself); with a delta x_out is required and may alias x */
 int lp_f32_layernorm_fwd(const float* x, const float* delta, float* x_out, const float* gamma, const float* beta, float eps, int M, int D,
                          int drop_T, float* y, float* mean, float* rstd, lp_stream_t stream);
 int lp_f32_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, int M, int D, int drop_T,
@@ -567,7 +569,9 @@ int lp_cam_pairwise_fwd_bwd(const float* targ_3d, const float* pred_3d, int B, i
 /* y (R,D) (+)= w (R,Q) @ x (Q,D), or with transpose_w: y (Q,D) (+)= w^T @ x (R,D): bicubic position-embedding interpolation */
 int lp_small_matmul(const float* w, const float* x, int R, int Q, int D, int transpose_w, int accumulate, float* y, lp_stream_t stream);
 /* x_out = x (+ delta_bf16);  y = LayerNorm(x_out) in bf16;  drop_T > 0: rows with row % drop_T == 0 ([CLS]) are dropped from y and
- * the rest compacted (the (B, h, w, D) feature map).  x_out may alias x; mean / rstd (M,) are kept for the backward pass. */
+ * the rest compacted (the (B, h, w, D) feature map).  x_out may alias x; mean / rstd (M,) are kept for the backward pass.
+ * x_out is required with a delta and optional without one: a non-NULL x_out then receives a copy of x.  (The fp32 form
+ * lp_f32_layernorm_fwd differs there: without a delta it never writes x_out.) */
 int lp_layernorm_fwd(const float* x, const void* delta_bf16, float* x_out, const float* gamma, const float* beta, float eps, int M,
                      int D, int drop_T, void* y_bf16, float* mean, float* rstd, lp_stream_t stream);
 /* dx_acc += LayerNorm backward of dy (bf16, same row mapping as y);  dgamma_acc / dbeta_acc accumulate too */

@@ -1,10 +1,11 @@
-"""float64 references of the step's contractions (convolutions, GEMMs, attention), computed from the same bf16 operands the kernels read.
+"""float64 references of the step's contractions (convolutions, GEMMs, attention), computed from the same bf16 (or, for the fp32 validation
+kernels, fp32) operands the kernels read.
 
 Everything here runs in torch float64 on the operands' device: im2col (F.unfold) and torch.matmul, never an fp32 library convolution or GEMM
 (those may take reduced-precision paths).  Beside every result r the helpers return S = sum |a b| over the products behind it (the same
 matmul on |A| and |B|): the scale of the rounding error an fp32-accumulating kernel may make, whatever the signs.
 
-Used by tests/test_step_contractions_fp64.py.
+Used by tests/test_step_contractions_fp64.py and, from "fp32 validation kernels" down, by tests/test_fp32_validation_kernels.py.
 """
 
 from __future__ import annotations
@@ -167,3 +168,106 @@ def gelu(x: torch.Tensor) -> torch.Tensor:
 
 def gelu_grad(x: torch.Tensor) -> torch.Tensor:
     return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+
+
+# ---------------------------------------------------------------------------------------------------------------- fp32 validation kernels
+# Written-out float64 forms of what csrc/fp32.hip / csrc/vit_f32.hip compute, on the same fp32 operands.  Where a result is a sum of
+# products the helper also returns S = the same expression on absolute values (the scale of f32_bar).
+def conv_weight_dgrad_from_storage(w: torch.Tensor, R: int, S: int, Ci: int) -> torch.Tensor:
+    """[Co][KH][KW][CiS] storage -> the (Ci, Co R S) matrix of weight_matrix_dgrad (no transposed copy exists on the fp32 path)"""
+    return weight_matrix_dgrad(w[:, :R, :S, :Ci].permute(3, 1, 2, 0), R, S)
+
+
+def conv_wgrad(A: torch.Tensor, dy: torch.Tensor, Co: int, Ci: int, R: int, S: int):
+    """dW[n][r][s][c] = sum_m A[m][(c, r, s)] dy[m][n] from im2col rows A (M, Ci R S): -> (dW, S) as (Co, R, S, Ci)"""
+    d = dy.reshape(-1, Co).to(F64)
+    shape = lambda t: t.reshape(Co, Ci, R, S).permute(0, 2, 3, 1)  # noqa: E731
+    return shape(d.T @ A), shape(d.abs().T @ A.abs())
+
+
+def attn_split(qkv: torch.Tensor, B: int, nh: int, T: int, k_off: int, v_off: int):
+    """fused (B T, ld) tensor -> q, k, v (B, nh, T, 64) float64"""
+    t = qkv.reshape(B, T, -1).to(F64)
+    cut = lambda o: t[:, :, o:o + nh * 64].reshape(B, T, nh, 64).permute(0, 2, 1, 3)  # noqa: E731
+    return cut(0), cut(k_off), cut(v_off)
+
+
+def attn_fwd(q, k, v, scale: float):
+    """-> (P, O, S_O): soft-max(scale q k^T), P v, |P| |v|"""
+    p = torch.softmax(scale * torch.einsum("bhid,bhjd->bhij", q, k), dim=-1)
+    return p, torch.einsum("bhij,bhjd->bhid", p, v), torch.einsum("bhij,bhjd->bhid", p, v.abs())
+
+
+def attn_bwd(q, k, v, p, do, scale: float):
+    """dQ, dK, dV from the STORED probabilities p (an operand of the backward kernels) and their scales: every product behind an
+    element in absolute value, through the chain dP = dO V^T, dS = P o (dP - rowsum(P o dP))"""
+    dp = torch.einsum("bhid,bhjd->bhij", do, v)
+    dp_s = torch.einsum("bhid,bhjd->bhij", do.abs(), v.abs())
+    ds = p * (dp - (p * dp).sum(-1, keepdim=True))
+    ds_s = p * (dp_s + (p * dp_s).sum(-1, keepdim=True))
+    dq, dq_s = scale * torch.einsum("bhij,bhjd->bhid", ds, k), scale * torch.einsum("bhij,bhjd->bhid", ds_s, k.abs())
+    dk, dk_s = scale * torch.einsum("bhij,bhid->bhjd", ds, q), scale * torch.einsum("bhij,bhid->bhjd", ds_s, q.abs())
+    dv, dv_s = torch.einsum("bhij,bhid->bhjd", p, do), torch.einsum("bhij,bhid->bhjd", p, do.abs())
+    return (dq, dq_s), (dk, dk_s), (dv, dv_s)
+
+
+def heads_to_rows(t: torch.Tensor) -> torch.Tensor:
+    """(B, nh, T, 64) -> (B T, nh 64), the column block of a fused tensor"""
+    B, nh, T, _ = t.shape
+    return t.permute(0, 2, 1, 3).reshape(B * T, nh * 64)
+
+
+def kept_rows(M: int, drop_T: int, device, shift: int = 0) -> torch.Tensor:
+    """the rows a LayerNorm with drop_T writes, in output order: row % drop_T != 0 (shift = 1: the off-by-one mutant)"""
+    r = torch.arange(M, device=device)
+    return r if drop_T == 0 else r[(r % drop_T) != shift]
+
+
+def maxpool_windows(x: torch.Tensor) -> torch.Tensor:
+    """NHWC -> (B, C, 9, Ho Wo) float64 windows of the 3x3 / stride 2 / pad 1 pool, taps row-major, padding = -inf"""
+    B, H, W, C_ = x.shape
+    g = F.pad(x.to(F64).permute(0, 3, 1, 2), (1, 1, 1, 1), value=-math.inf)
+    return F.unfold(g, 3, stride=2).reshape(B, C_, 9, -1)
+
+
+def maxpool_fwd(x: torch.Tensor, last: bool = False):
+    """-> (max (B, Ho, Wo, C), tap of the FIRST maximum in row-major order as uint8; last=True: of the last one - the tie mutant)"""
+    B, H, W, C_ = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    win = maxpool_windows(x)
+    m = win.amax(2, keepdim=True)
+    taps = torch.arange(9, device=x.device).reshape(1, 1, 9, 1)
+    hit = win == m
+    arg = torch.where(hit, taps, torch.full_like(taps, -1 if last else 9))
+    arg = arg.amax(2) if last else arg.amin(2)
+    nhwc = lambda t: t.reshape(B, C_, Ho, Wo).permute(0, 2, 3, 1).contiguous()  # noqa: E731
+    return nhwc(m.squeeze(2)), nhwc(arg).to(torch.uint8)
+
+
+def maxpool_bwd(arg: torch.Tensor, dy: torch.Tensor, H: int, W: int):
+    """dx[pixel] = sum of the dy of the windows whose arg-max tap is that pixel: -> (dx, sum |dy| likewise), NHWC"""
+    B, Ho, Wo, C_ = dy.shape
+    onehot = (arg.permute(0, 3, 1, 2).reshape(B, C_, 1, -1).long() == torch.arange(9, device=dy.device).reshape(1, 1, 9, 1)).to(F64)
+    out = []
+    for d in (dy.to(F64), dy.to(F64).abs()):
+        cols = onehot * d.permute(0, 3, 1, 2).reshape(B, C_, 1, -1)
+        out.append(F.fold(cols.reshape(B, C_ * 9, -1), (H, W), 3, stride=2, padding=1).permute(0, 2, 3, 1).contiguous())
+    return out[0], out[1]
+
+
+def pixel_shuffle(x: torch.Tensor, c_out: int) -> torch.Tensor:
+    """(B, h, w, 4 c_out) -> (B, 2h, 2w, c_out): out[b][2y+i][2x+j][c] = in[b][y][x][4c + 2i + j]"""
+    B, h, w, _ = x.shape
+    return x.reshape(B, h, w, c_out, 2, 2).permute(0, 1, 4, 2, 5, 3).reshape(B, 2 * h, 2 * w, c_out)
+
+
+def pixel_unshuffle(x: torch.Tensor) -> torch.Tensor:
+    """the inverse: (B, 2h, 2w, c) -> (B, h, w, 4c)"""
+    B, H, W, c = x.shape
+    return x.reshape(B, H // 2, 2, W // 2, 2, c).permute(0, 1, 3, 5, 2, 4).reshape(B, H // 2, W // 2, 4 * c)
+
+
+def patchify(img: torch.Tensor, P: int) -> torch.Tensor:
+    """(B, 3, H, W) -> (B gh gw, 3 P P), k = (c, ky, kx)"""
+    B, _, H, W = img.shape
+    return img.reshape(B, 3, H // P, P, W // P, P).permute(0, 2, 4, 1, 3, 5).reshape(B * (H // P) * (W // P), 3 * P * P)
