@@ -51,8 +51,9 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * call (lightning_pose_amd/_lib.py raises LpHipUnavailable on a mismatch) - a library built against an older header would otherwise take,
  * e.g., the stream argument for an inserted flag without any error.  History: 131 = round 5 (decode `prune`, bn_bwd `terms_ws`), 140 = round 6,
  * 144 = the multi-view token assembly (lp_vit_mv_tokens_*), 145 = the camera geometry of the calibrated 3-D losses (lp_cam_*),
- * 146 = patch masking (lp_patch_mask_f32), 147 = LayerScale inside the LayerNorm walks (lp_layernorm_ls_*, the DINOv2 backbones). */
-#define LP_HIP_ABI_VERSION 147
+ * 146 = patch masking (lp_patch_mask_f32), 147 = LayerScale inside the LayerNorm walks (lp_layernorm_ls_*, the DINOv2 backbones),
+ * 148 = the multi-view labeled batch with its 3-D augmentation (lp_mv3d_*). */
+#define LP_HIP_ABI_VERSION 148
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -735,6 +736,52 @@ int lp_labelaug_keypoints(const float* kp, int B, int K, const float* affine, co
  * ------------------------------------------------------------------------------------------------------ */
 int lp_patch_mask_f32(const float* images, int BV, int C, int H, int W, int patch, int count, unsigned long long key, const float* mask_in,
                       float* out, float* mask_out, lp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Multi-view labeled batches with the 3-D augmentation (csrc/mv3d.hip; reference data/datasets.py:853-1104,
+ * MultiviewHeatmapDataset.apply_3d_transforms and what it calls).  All fp32 unless said otherwise.
+ *
+ * lp_mv3d_plan: ONE launch for the batch, one workgroup per sample, no workspace, no atomics, every median a rank selection and every
+ * sum in a fixed order: the same input gives the same bits.
+ *   kp (B, V, K, 2) labels in stored-image px, NaN = unlabeled; src_hw (B, V, 2) stored image (height, width); bbox (B, 4 V) [x, y, h, w]
+ *   per view; intrinsics / extrinsics / dist12 as for lp_cam_*; draws (B, 4) = [scale, r_x, r_y, r_z] drawn by the caller.
+ *   1. frame px: u = x / ws * bw + bx, v = y / hs * bh + by.
+ *   2. undistort + triangulate every pair (lp_cam_chain_fwd's arithmetic; a pair with a NaN point is NaN); X[k] = numpy's nanmedian over
+ *      the pairs per coordinate (an even count: the mean of the two middle values; all NaN: NaN).
+ *   3. status 2: every kp coordinate is NaN.  status 1: augment == 0, or fewer than 3 keypoints with a non-NaN X.  In both
+ *      kp3d = X, kp2d = the labels in model px (x / ws * W, y / hs * H, NaN kept), affine = identity.
+ *   4. otherwise med = nanmedian_k X; X' = (X - med) scale + med; extent = nanmax_k X' - nanmin_k X'; X' += shift_param extent r;
+ *      q = X' projected into every view in frame px (lp_cam_project_fwd without a bbox; a NaN X' gives NaN).
+ *   5. per view the least-squares similarity M_v = [[a, -b, t_x], [b, a, t_y]], stored px -> warped px, of o = kp onto
+ *      n = ((q_x - bx) / bw ws, (q_y - by) / bh hs) over the keypoints finite in both: with o', n' centred on their means,
+ *      a = sum o' . n' / sum |o'|^2, b = sum (o'_x n'_y - o'_y n'_x) / sum |o'|^2, t = mean n - R mean o; a zero denominator: identity.
+ *      This is what cv2.estimateAffinePartial2D returns when every point is an inlier, up to its refinement tolerance (UNPINNED: cv2 is
+ *      not a dependency).  Fewer than 3 matched keypoints in ANY view: status 3 and the outputs of status 1 for the whole sample - the
+ *      reference raises RuntimeError("... should have been caught earlier") there.
+ *   6. status 0: kp3d = X', kp2d = ((q_x - bx) / bw W, (q_y - by) / bh H) (not clipped), affine = M.
+ *   kp3d (B, K, 3), kp2d (B, V, K, 2), affine (B, V, 2, 3), status (B) int32.  2 <= V <= LP_MV3D_MAX_VIEWS, K <= LP_MV3D_MAX_KEYPOINTS,
+ *   B <= 65535 (LP_ERR_UNSUPPORTED otherwise); a null pointer or a non-positive dimension: LP_ERR_ARGUMENT.
+ *
+ * lp_mv3d_fill: src_u8 (B, Hs, Ws, 3) contiguous -> fill (B) = min over pixels and channels of (v / 255 - mean_c) / std_c (the reference
+ * pads the warp with orig_img.min() of the normalised image).  One workgroup per sample.  std must be > 0.
+ *
+ * lp_mv3d_finish: normalise -> warp_affine(M, bilinear, align_corners=True, padding_mode="fill", same size) -> resize to (H, W)
+ * (bilinear, half-pixel centres, no antialiasing, clamped taps: torch.nn.functional.interpolate's arithmetic) in ONE pass for ONE view:
+ * output pixel (y, x) takes its 4 resize taps at integer warped pixels (X, Y); each tap is the bilinear sample of the normalised source
+ * at M^-1 (X, Y) in pixel-index coordinates, a neighbour outside the image reading fill[b] (kornia's mask blend).  The warped image is
+ * never written; M is inverted once per image (a singular or NaN M gives fill everywhere).  src_u8 (B, Hs, Ws, 3) is view v's images;
+ * affine (B, V, 2, 3) is lp_mv3d_plan's output, row (b, v) is used; dst (B, V, 3, H, W): only [:, v] is written (16-byte stores when
+ * W % 4 == 0 and dst is 16-byte aligned).  Views may differ in (Hs, Ws): one launch per view.  An identity M gives the plain resize of
+ * the normalised image bit for bit (products and sums are not contracted).
+ * ------------------------------------------------------------------------------------------------------ */
+#define LP_MV3D_MAX_VIEWS 8
+#define LP_MV3D_MAX_KEYPOINTS 128
+int lp_mv3d_plan(const float* kp, const float* src_hw, const float* bbox, const float* intrinsics, const float* extrinsics,
+                 const float* dist12, const float* draws, int augment, float shift_param, int H, int W, int B, int V, int K, float* kp3d,
+                 float* kp2d, float* affine, int* status, lp_stream_t stream);
+int lp_mv3d_fill(const void* src_u8, int B, int Hs, int Ws, const lp_frame_norm* norm, float* fill, lp_stream_t stream);
+int lp_mv3d_finish(const void* src_u8, int B, int Hs, int Ws, const float* affine, const float* fill, const lp_frame_norm* norm, int V,
+                   int v, int H, int W, float* dst, lp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Optimiser: torch.optim.Adam / AdamW semantics (models/base.py:458-479) over one flat fp32 range, also emitting

@@ -63,7 +63,7 @@ AUG_LOCAL_BLUR_COARSE, AUG_LOCAL_EMBOSS = 0, 1
 AUG_ELASTIC_MAX_RADIUS = 20
 TF_NONE, TF_SINGLE, TF_PER_FRAME, TF_PER_VIEW = 0, 1, 2, 3
 
-ABI_VERSION = 147   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
+ABI_VERSION = 148   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -178,6 +178,9 @@ PROTOTYPES = {
     "lp_labelaug_finish": (_I, [_P, _I, _I, _I, _P, _I, _I, C.POINTER(FrameNorm), _P, _P]),
     "lp_labelaug_keypoints": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
     "lp_patch_mask_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_ulonglong, _P, _P, _P, _P]),
+    "lp_mv3d_plan": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "lp_mv3d_fill": (_I, [_P, _I, _I, _I, C.POINTER(FrameNorm), _P, _P]),
+    "lp_mv3d_finish": (_I, [_P, _I, _I, _I, _P, _P, C.POINTER(FrameNorm), _I, _I, _I, _I, _P, _P]),
     "lp_f32_conv_fwd": (_I, [_P, _P, C.POINTER(ConvGeom), _I, _I, _I, _P, _P, _P, _P]),
     "lp_f32_conv_dgrad": (_I, [_P, _P, C.POINTER(ConvGeom), _I, _I, _I, _P, _P, _P, _P]),
     "lp_f32_conv_wgrad": (_I, [_P, _P, C.POINTER(ConvGeom), _I, _I, _I, _P, _P]),

@@ -13,6 +13,10 @@ optional flip with the left / right swap, out-of-frame -> NaN, Gaussian targets)
 ``data.augmentations.imgaug_transform`` / ``get_imgaug_transform`` build from ``cfg.training.imgaug`` (the reference's ``iaa.Sequential``
 in the same argument): it is drawn once per batch on the host and applied to the uint8 images on the device before the resize; the
 validation / test / prediction loaders ask for ``augment=False``.  Context (5-frame) loading is outside this path.
+
+``MultiviewHeatmapDataset`` (reference :553-1228) holds one ``HeatmapDataset`` per view, the per-view bounding-box files and the anipose
+calibration of every frame, and hands ``MultiviewLabeledBatchProducer`` whole batches: with a calibration, a training batch goes through the
+reference's 3-D augmentation (``apply_3d_transforms``) on the device.
 """
 
 from __future__ import annotations
@@ -25,8 +29,12 @@ import numpy as np
 import pandas as pd
 import torch
 
-from .datatypes import HeatmapLabeledBatchDict
-from .producers import HostStager, LabeledBatchProducer
+from pathlib import Path
+
+from .augmentations import LabeledAugmentation
+from .cameras import CameraGroup
+from .datatypes import HeatmapLabeledBatchDict, MultiviewHeatmapLabeledBatchDict
+from .producers import HostStager, LabeledBatchProducer, MultiviewLabeledBatchProducer
 
 
 @dataclass
@@ -158,6 +166,202 @@ class HeatmapDataset:
                              hflip=hflip, augment=drawn)
 
     def batches(self, batch_size: int, shuffle: bool = True, seed: int = 0, drop_last: bool = False) -> Iterator[HeatmapLabeledBatchDict]:
+        order = np.random.default_rng(seed).permutation(len(self)) if shuffle else np.arange(len(self))
+        for lo in range(0, len(order), batch_size):
+            chunk = order[lo:lo + batch_size]
+            if drop_last and len(chunk) < batch_size:
+                return
+            yield self.batch(chunk.tolist())
+
+
+class MultiviewHeatmapDataset:
+    """One ``HeatmapDataset`` per camera view at ``self.dataset[view]``; batches of all views built on the device.
+
+    Constructor arguments in the reference's order and meaning (data/datasets.py:571-617); ``resize`` is accepted and has nothing to do (the
+    resize is always the last step of the device path); ``imgaug_hflip`` is always False (not supported for multi-view).  ``imgaug_transform``
+    is the ``LabeledAugmentation`` of ``cfg.training.imgaug``: with a calibration it must hold pixel operators only (the "dlc-mv" preset) -
+    the geometry is the 3-D augmentation's.  The reference augments in 3-D when the imgaug pipeline has no Resize (training) and only
+    triangulates otherwise; here ``batch(..., augment=True / False)`` says which, as for ``HeatmapDataset``."""
+
+    def __init__(self, root_directory: str, csv_paths: list[str], view_names: list[str], image_resize_height: int, image_resize_width: int,
+                 header_rows: list[int] | None = [0, 1, 2], imgaug_transform=None, downsample_factor: int = 2, do_context: bool = False,
+                 resize: bool = False, uniform_heatmaps: bool = False, camera_params_path: str | None = None,
+                 bbox_paths: list[str] | None = None, device: torch.device | str | None = None) -> None:
+        if len(view_names) != len(csv_paths):
+            raise ValueError("number of names does not match with the number of files!")
+        if do_context:
+            raise NotImplementedError("context (5-frame) datasets belong to the MHCRNN models, outside the MI355X heatmap-tracker path")
+        self.imgaug_hflip = False
+        self.root_directory = str(root_directory)
+        self.csv_paths = list(csv_paths)
+        self.bbox_paths = list(bbox_paths) if bbox_paths else [None] * len(view_names)
+        if len(self.bbox_paths) != len(view_names):
+            raise ValueError("zip() argument: bbox_paths must have one entry per view")   # (the reference's zip(..., strict=True))
+        self.view_names = list(view_names)
+        self.image_resize_height, self.image_resize_width = int(image_resize_height), int(image_resize_width)
+        self.do_context = False
+        self.resize = bool(resize)
+        # (never None: BaseDataModule asks for augment=False on validation / test batches of a dataset that HAS a transform, and the 3-D
+        # augmentation is one; an empty pipeline is 'resize only')
+        self.imgaug_transform = imgaug_transform if imgaug_transform is not None else LabeledAugmentation([])
+        self.downsample_factor = int(downsample_factor)
+        self.uniform_heatmaps = bool(uniform_heatmaps)
+        self.device = torch.device(device) if device is not None else torch.device(f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}")
+        self.dataset: dict[str, HeatmapDataset] = {}
+        self.keypoint_names: dict[str, list[str]] = {}
+        self.bboxes: dict[str, np.ndarray | None] = {}
+        data_length_by_view, num_keypoints_by_view = {}, {}
+        for view, csv_path, bbox_path in zip(self.view_names, self.csv_paths, self.bbox_paths):
+            ds = HeatmapDataset(root_directory=root_directory, csv_path=csv_path, image_resize_height=image_resize_height,
+                                image_resize_width=image_resize_width, header_rows=header_rows, imgaug_transform=imgaug_transform,
+                                downsample_factor=downsample_factor, do_context=False, uniform_heatmaps=uniform_heatmaps, device=self.device)
+            self.dataset[view] = ds
+            self.keypoint_names[view] = ds.keypoint_names
+            data_length_by_view[view] = len(ds)
+            num_keypoints_by_view[view] = ds.num_keypoints
+            self.bboxes[view] = self._load_bboxes(bbox_path, ds.image_names)
+        self.num_keypoints = sum(num_keypoints_by_view.values())
+        self.check_data_images_names(data_length_by_view)
+        self.num_targets = self.num_keypoints * 2
+        if camera_params_path is not None:
+            self.cam_params_df, self.cam_params_file_to_camgroup = self._load_cam_params_from_csv(camera_params_path)
+        else:
+            self.cam_params_df, self.cam_params_file_to_camgroup = self._discover_cam_params_from_image_paths()
+        self.producer = MultiviewLabeledBatchProducer(image_resize_height, image_resize_width, downsample_factor=downsample_factor,
+                                                      uniform_heatmaps=uniform_heatmaps)
+        self._rigs: dict[str, tuple] = {}   # calibration file -> host (intrinsics, extrinsics, distortions) of one sample
+
+    # ---- files ------------------------------------------------------------------------------------------------------------------
+    def _load_bboxes(self, bbox_path: str | None, image_names: list[str]) -> np.ndarray | None:
+        """(image_path, x, y, h, w) rows in the order of the label file (reference :189-201)"""
+        if not bbox_path:
+            return None
+        bbox_file = bbox_path if os.path.isfile(bbox_path) else os.path.join(self.root_directory, bbox_path)
+        if not os.path.exists(bbox_file):
+            raise FileNotFoundError(f"Could not find bbox file at {bbox_file}!")
+        df = pd.read_csv(bbox_file, header=[0], index_col=0)
+        assert df.index.tolist() == image_names
+        return df.to_numpy().astype(np.float32)
+
+    def _load_camgroup(self, calib_file: str) -> CameraGroup:
+        camgroup = CameraGroup.load(os.path.join(self.root_directory, calib_file), device=self.device)
+        cam_names = camgroup.get_names()
+        assert list(cam_names) == list(self.view_names), (
+            "cfg.data.view_names must have same camera order as camera calibration file; "
+            f"instead found {self.view_names} and {cam_names}.")
+        return camgroup
+
+    def _load_cam_params_from_csv(self, camera_params_path: str):
+        """a CSV that maps every frame to a calibration TOML (reference :702-724)"""
+        path = camera_params_path if os.path.isfile(camera_params_path) else os.path.join(self.root_directory, camera_params_path)
+        cam_params_df = pd.read_csv(path, index_col=0, header=[0])
+        img_idxs_labels = [i.split("/")[-1] for i in self.dataset[self.view_names[0]].image_names]
+        img_idxs_calib = [i.split("/")[-1] for i in cam_params_df.index]
+        assert img_idxs_labels == img_idxs_calib
+        return cam_params_df, {f: self._load_camgroup(f) for f in cam_params_df.file.unique()}
+
+    def _discover_cam_params_from_image_paths(self):
+        """labeled-data/<session>_<view>/img<frameidx>.ext -> calibrations/<session>.toml, then calibration.toml (reference :726-786);
+        (None, None) if no calibration is found, or not for every frame"""
+        image_names = self.dataset[self.view_names[0]].image_names
+        groups: dict[str, CameraGroup] = {}
+        calib_files, all_found = [], True
+        for img_name in image_names:
+            parts = Path(img_name).parts
+            if "labeled-data" not in parts:
+                raise ValueError(f"Image path '{img_name}' does not match expected pattern labeled-data/<session>_<view>/img<frameidx>.ext")
+            folder_name = parts[parts.index("labeled-data") + 1]
+            if "_" not in folder_name:
+                raise ValueError(f"Folder '{folder_name}' in image path '{img_name}' does not match expected pattern <session>_<view>")
+            session_id = folder_name.rsplit("_", 1)[0]
+            if (Path(self.root_directory) / "calibrations" / f"{session_id}.toml").exists():
+                calib_file = str(Path("calibrations") / f"{session_id}.toml")
+            elif (Path(self.root_directory) / "calibration.toml").exists():
+                calib_file = "calibration.toml"
+            else:
+                all_found = False
+                calib_files.append(None)
+                continue
+            calib_files.append(calib_file)
+            if calib_file not in groups:
+                groups[calib_file] = self._load_camgroup(calib_file)
+        if groups and all_found:
+            return pd.DataFrame({"file": calib_files}, index=image_names), groups
+        return None, None   # (some frames without a calibration: 3-D is off for the whole dataset, as in the reference)
+
+    def check_data_images_names(self, data_length_by_view: dict[str, int]) -> None:
+        """the label files must agree in rows, keypoint order and image file names (reference :788-820)"""
+        if len(set(data_length_by_view.values())) != 1:
+            raise ImportError("the CSV files do not match in row numbers!")
+        first = self.keypoint_names[self.view_names[0]]
+        for key_num, keypoint in enumerate(first):
+            for view, names in self.keypoint_names.items():
+                if key_num >= len(names) or keypoint != names[key_num]:
+                    raise ImportError(f"the keypoints are not in correct order! view: {self.view_names[0]} vs {view} | {keypoint} != {names}")
+        self.data_length = list(data_length_by_view.values())[0]
+        for idx in range(self.data_length):
+            names = {Path(ds.image_names[idx]).name for ds in self.dataset.values()}
+            if len(names) > 1:
+                raise ImportError(f"Discrepancy in image file names across CSV files! index:{idx}, image file names:{names}")
+
+    # ---- attributes -------------------------------------------------------------------------------------------------------------
+    @property
+    def height(self) -> int:
+        return self.image_resize_height
+
+    @property
+    def width(self) -> int:
+        return self.image_resize_width
+
+    @property
+    def output_shape(self) -> tuple[int, int]:
+        return self.height // 2 ** self.downsample_factor, self.width // 2 ** self.downsample_factor
+
+    @property
+    def num_views(self) -> int:
+        return len(self.view_names)
+
+    def __len__(self) -> int:
+        return self.data_length
+
+    # ---- batches ----------------------------------------------------------------------------------------------------------------
+    def _rig(self, calib_file: str):
+        if calib_file not in self._rigs:
+            self._rigs[calib_file] = tuple(t[0] for t in self.cam_params_file_to_camgroup[calib_file].rig(1, device="cpu"))
+        return self._rigs[calib_file]
+
+    def batch(self, indices: Sequence[int], hflip: torch.Tensor | None = None, augment: bool = True,
+              params: np.ndarray | None = None) -> MultiviewHeatmapLabeledBatchDict:
+        """The labeled batch of these examples.  ``augment=True``: the pixel operators of ``imgaug_transform`` per view and, with a
+        calibration, the 3-D augmentation (``params`` (B, 4) overrides its draw); ``augment=False``: resize only (validation, test,
+        prediction), ``keypoints_3d`` the plain triangulation.  ``hflip`` must be None: multi-view flips are not supported."""
+        if hflip is not None and bool(torch.as_tensor(hflip).any()):
+            raise ValueError("imgaug_hflip is not supported for multi-view datasets")
+        idx = torch.as_tensor(list(indices), dtype=torch.long)
+        views = [self.dataset[v] for v in self.view_names]
+        images = [ds._stage(ds.load_images(idx.tolist())) for ds in views]
+        kp = torch.stack([ds.keypoints[idx] for ds in views], dim=1)            # (B, V, K, 2)
+        vis = torch.stack([ds.visibility[idx] for ds in views], dim=1)          # (B, V, K)
+        rows = []
+        for ds, view, im in zip(views, self.view_names, images):
+            bb = self.bboxes[view]
+            rows.append(torch.tensor([0.0, 0.0, float(im.shape[1]), float(im.shape[2])]).repeat(len(idx), 1) if bb is None
+                        else torch.from_numpy(bb[idx.numpy()]))
+        bbox = torch.cat(rows, dim=1)                                           # (B, 4 V)
+        rig = {}
+        if self.cam_params_file_to_camgroup:
+            per = [self._rig(self.cam_params_df.iloc[int(i)].file) for i in idx]
+            n = max(p[2].shape[-1] for p in per)
+            rig = dict(intrinsics=torch.stack([p[0] for p in per]), extrinsics=torch.stack([p[1] for p in per]),
+                       distortions=torch.stack([torch.nn.functional.pad(p[2], (0, n - p[2].shape[-1])) for p in per]))
+        drawn = None
+        tf = self.imgaug_transform
+        if augment and tf is not None and len(tf) > 0:
+            drawn = [tf.draw(len(idx), int(im.shape[1]), int(im.shape[2])) for im in images]
+        return self.producer(images, kp, self.view_names, idxs=idx, visibility=vis, bbox=bbox, augment=augment, params=params,
+                             pixel_augment=drawn, **rig)
+
+    def batches(self, batch_size: int, shuffle: bool = True, seed: int = 0, drop_last: bool = False) -> Iterator[MultiviewHeatmapLabeledBatchDict]:
         order = np.random.default_rng(seed).permutation(len(self)) if shuffle else np.arange(len(self))
         for lo in range(0, len(order), batch_size):
             chunk = order[lo:lo + batch_size]

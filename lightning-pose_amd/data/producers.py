@@ -12,12 +12,21 @@
                          out-of-frame -> NaN, visibility synthesis, Gaussian targets (``lp_heatmap_gen``) -> ``HeatmapLabeledBatchDict``
                          with nothing but the uint8 images crossing PCIe.
 
+``MultiviewLabeledBatchProducer``
+                         the per-sample work of ``MultiviewHeatmapDataset.__getitem__`` / ``apply_3d_transforms`` (data/datasets.py:853-1228)
+                         for a whole batch: triangulation, the random 3-D scale and translation, reprojection and the per-view
+                         similarity in ONE launch (``lp_mv3d_plan``), then per view the padding value and normalise -> warp -> resize
+                         fused (``lp_mv3d_fill``, ``lp_mv3d_finish``), then the Gaussian targets -> ``MultiviewHeatmapLabeledBatchDict``.
+
 ``FrameWindowSource``   the sequencing half of ``fn.readers.video`` for already-decoded videos (windows of ``sequence_length`` frames every
                          ``step`` frames, seeded shuffling per rank, zero-padded tails) with the host -> device copy of the next window
                          overlapping the step on the current one (pinned staging, copy stream).
 
 The image operators are restatements of DALI's / imgaug's published definitions (neither library is available to check against):
 parity of pixel values is UNPINNED; keypoints, visibility and targets are pinned against the verbatim reference dataset.
+The multi-view producer adds two unpinned points of the same kind: its per-view similarity is the closed-form least-squares fit, which is
+what ``cv2.estimateAffinePartial2D`` (RANSAC + refinement) returns when every point is an inlier, up to cv2's refinement tolerance; and its
+pixels restate kornia's ``warp_affine`` / ``resize`` (neither cv2 nor kornia is available to check against).
 """
 
 from __future__ import annotations
@@ -30,7 +39,7 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
-from .datatypes import HeatmapLabeledBatchDict, MultiviewUnlabeledBatchDict, UnlabeledBatchDict
+from .datatypes import HeatmapLabeledBatchDict, MultiviewHeatmapLabeledBatchDict, MultiviewUnlabeledBatchDict, UnlabeledBatchDict
 
 _IMAGENET_MEAN = [0.485, 0.456, 0.406]  # reference data/__init__.py:46-47
 _IMAGENET_STD = [0.229, 0.224, 0.225]
@@ -215,6 +224,126 @@ class LabeledBatchProducer:
         if idxs is None:
             idxs = torch.arange(b)
         return HeatmapLabeledBatchDict(images=images, keypoints=kp_model.reshape(b, 2 * k), heatmaps=heatmaps, bbox=bbox.to(dev), idxs=idxs)
+
+
+class MultiviewLabeledBatchProducer:
+    """Per-view uint8 labeled images + stored labels (+ a calibration) -> the labeled batch of the multi-view trackers, built on the device.
+
+    With a calibration and ``augment=True`` the batch goes through the reference's 3-D augmentation: a fixed number of launches (one
+    ``lp_mv3d_plan``, one ``lp_mv3d_fill`` + ``lp_mv3d_finish`` per view, one ``lp_heatmap_gen``), nothing read back, no host <-> device
+    synchronisation.  Without a calibration, or with ``augment=False``, every view takes ``LabeledBatchProducer``'s path (what
+    ``HeatmapDataset`` does), and with a calibration ``keypoints_3d`` is the plain triangulation.
+
+    One deviation from the reference: a sample in which some view keeps fewer than 3 keypoints that are labeled AND reproject to a finite
+    point is handed over unaugmented (``lp_mv3d_plan`` status 3); the reference raises ``RuntimeError("Fewer than 3 valid keypoints in 3d
+    data augmentation; this error should have been caught earlier!")`` there."""
+
+    def __init__(self, image_resize_height: int, image_resize_width: int, downsample_factor: int = 2, uniform_heatmaps: bool = False,
+                 normalization_mean: Sequence[float] = _IMAGENET_MEAN, normalization_std: Sequence[float] = _IMAGENET_STD, seed: int = 123456,
+                 scale_params: Sequence[float] = (0.8, 1.2), shift_param: float = 0.25) -> None:
+        self.view = LabeledBatchProducer(image_resize_height, image_resize_width, downsample_factor=downsample_factor,
+                                         uniform_heatmaps=uniform_heatmaps, normalization_mean=normalization_mean,
+                                         normalization_std=normalization_std)
+        self.height, self.width = self.view.height, self.view.width
+        self.mean, self.std = list(normalization_mean), list(normalization_std)
+        self.scale_params = (float(scale_params[0]), float(scale_params[1]))
+        self.shift_param = float(shift_param)
+        self.seed = int(seed) + int(os.environ.get("LOCAL_RANK", "0"))
+        self._rng = np.random.default_rng(self.seed)
+        self.last_plan: dict | None = None   # the device tensors of the last augmented batch's plan (affine, status): tests, logging
+
+    @property
+    def output_shape(self) -> tuple[int, int]:
+        return self.view.output_shape
+
+    def draw(self, b: int) -> np.ndarray:
+        """(b, 4) float32 [scale, r_x, r_y, r_z]: scale U(scale_params), r U(-1, 1) (reference data/datasets.py:870-877)"""
+        r = self._rng
+        return np.concatenate([r.uniform(*self.scale_params, size=(b, 1)), r.uniform(-1.0, 1.0, size=(b, 3))], axis=1).astype(np.float32)
+
+    def __call__(self, images_u8: Sequence[torch.Tensor], keypoints: torch.Tensor, view_names: Sequence[str], idxs: torch.Tensor | None = None,
+                 visibility: torch.Tensor | None = None, bbox: torch.Tensor | None = None, intrinsics: torch.Tensor | None = None,
+                 extrinsics: torch.Tensor | None = None, distortions: torch.Tensor | None = None, augment: bool = True,
+                 params: np.ndarray | torch.Tensor | None = None, pixel_augment: Sequence[dict | None] | None = None
+                 ) -> MultiviewHeatmapLabeledBatchDict:
+        """images_u8: one (B, Hs_v, Ws_v, 3) uint8 device tensor per view (views may differ in size); keypoints (B, V, K, 2) in stored px
+        (NaN = unlabeled); visibility (B, V, K) in {0, 1, 2} or None (synthesised from the NaN labels); bbox (B, 4 V) [x, y, h, w] per view
+        or None (the whole frames); intrinsics (B, V, 3, 3), extrinsics (B, V, 3, 4), distortions (B, V, n) or None (no calibration).
+        ``params`` (B, 4) overrides the 3-D draw; ``pixel_augment``: per view one draw of a ``LabeledAugmentation`` of pixel operators
+        (the "dlc-mv" preset), applied to that view's uint8 images first."""
+        v = len(images_u8)
+        if v < 2 or len(view_names) != v:
+            raise ValueError(f"{v} views of images, {len(view_names)} view names (at least 2, equally many)")
+        dev = images_u8[0].device
+        b = int(images_u8[0].shape[0])
+        kp = keypoints.to(dev).reshape(b, v, -1, 2).float()
+        k = int(kp.shape[2])
+        calibrated = intrinsics is not None
+        if calibrated and (extrinsics is None or distortions is None):
+            raise ValueError("a calibration is intrinsics, extrinsics and distortions together")
+        if bbox is None:
+            bbox = torch.tensor([c for im in images_u8 for c in (0.0, 0.0, float(im.shape[1]), float(im.shape[2]))]).repeat(b, 1)
+        bbox = bbox.to(dev).float()
+        if tuple(bbox.shape) != (b, 4 * v):
+            raise ValueError(f"bbox must be {(b, 4 * v)}, got {tuple(bbox.shape)}")
+        if idxs is None:
+            idxs = torch.arange(b)
+        if visibility is None:
+            vis = None
+        else:
+            vis = visibility.to(dev).reshape(b, v, k)
+        if pixel_augment is not None and len(pixel_augment) != v:
+            raise ValueError(f"pixel_augment has {len(pixel_augment)} entries for {v} views")
+        src_hw = torch.tensor([[float(im.shape[1]), float(im.shape[2])] for im in images_u8]).repeat(b, 1, 1).to(dev)   # (B, V, 2)
+        rig = dict(intrinsic_matrix=intrinsics, extrinsic_matrix=extrinsics, distortions=distortions)
+        if calibrated:
+            rig = {n: t.to(dev).float() for n, t in rig.items()}
+        else:   # the reference's placeholders (data/datasets.py:1203-1208), batched
+            rig = dict(intrinsic_matrix=torch.eye(3).repeat(b, 1, 1, 1).to(dev), extrinsic_matrix=torch.zeros(b, 1, 3, 4, device=dev),
+                       distortions=torch.zeros(b, 1, 5, device=dev))
+        common = dict(bbox=bbox, idxs=idxs, num_views=torch.full((b,), v), concat_order=list(view_names), view_names=list(view_names), **rig)
+
+        if not (calibrated and augment):
+            per_view = [self.view(images_u8[j], kp[:, j], idxs=idxs, visibility=None if vis is None else vis[:, j],
+                                  bbox=bbox[:, 4 * j:4 * j + 4], augment=None if pixel_augment is None else pixel_augment[j]) for j in range(v)]
+            images = torch.stack([d["images"] for d in per_view], dim=1)
+            kp_model = torch.stack([d["keypoints"].reshape(b, k, 2) for d in per_view], dim=1)
+            heatmaps = torch.cat([d["heatmaps"] for d in per_view], dim=1)
+            if calibrated:
+                kp3d = ops.mv3d_plan(kp, src_hw, bbox, rig["intrinsic_matrix"], rig["extrinsic_matrix"], rig["distortions"],
+                                     torch.zeros(b, 4, device=dev), self.height, self.width, augment=False)[0]
+            else:
+                kp3d = torch.ones(b, 1, device=dev)
+            self.last_plan = None
+            return MultiviewHeatmapLabeledBatchDict(images=images, keypoints=kp_model.reshape(b, 2 * v * k), heatmaps=heatmaps, keypoints_3d=kp3d,
+                                                    **common)
+
+        draws = self.draw(b) if params is None else params
+        draws = (torch.from_numpy(np.asarray(draws, dtype=np.float32)) if not torch.is_tensor(draws) else draws.float()).reshape(b, 4).to(dev)
+        raws = []
+        for j in range(v):
+            drawn = None if pixel_augment is None else pixel_augment[j]
+            if drawn is None:
+                raws.append(images_u8[j])
+                continue
+            moving = _lib.AUG_GEOM | _lib.AUG_ELASTIC | _lib.AUG_CROPPAD
+            if int(np.bitwise_or.reduce(drawn["table"]["flags"])) & moving:
+                raise NotImplementedError("the 3-D augmentation takes pixel operators only (the 'dlc-mv' preset): an operator that moves pixels "
+                                          "would leave the labels behind")
+            raws.append(drawn["pipeline"].run(images_u8[j], drawn)[0])
+        kp3d, kp2d, affine, status = ops.mv3d_plan(kp, src_hw, bbox, rig["intrinsic_matrix"], rig["extrinsic_matrix"], rig["distortions"], draws,
+                                                   self.height, self.width, augment=True, shift_param=self.shift_param)
+        images = torch.empty(b, v, 3, self.height, self.width, device=dev, dtype=torch.float32)
+        for j in range(v):   # views may differ in native size: one launch pair per view, each writing its own slice
+            ops.mv3d_finish(raws[j], affine, ops.mv3d_fill(raws[j], self.mean, self.std), self.mean, self.std, j, images)
+        if vis is None:   # HeatmapDataset's synthesis (reference :465-472) from the stored labels
+            nan = torch.isnan(kp[..., 0])
+            vis = torch.where(nan, torch.full_like(nan, 1 if self.view.uniform_heatmaps else 0, dtype=torch.int32),
+                              torch.full_like(nan, 2, dtype=torch.int32))
+        heatmaps = ops.generate_heatmaps(kp2d.reshape(b, v * k, 2), self.height, self.width, self.output_shape, self.view.output_sigma,
+                                         vis.reshape(b, v * k))   # the visibility goes in unchanged (reference :1099)
+        self.last_plan = {"affine": affine, "status": status, "draws": draws}
+        return MultiviewHeatmapLabeledBatchDict(images=images, keypoints=kp2d.reshape(b, 2 * v * k), heatmaps=heatmaps, keypoints_3d=kp3d, **common)
 
 
 class HostStager:

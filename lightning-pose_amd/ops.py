@@ -20,7 +20,7 @@ from ._lib import LpHipUnavailable, check
 
 __all__ = [
     "decode", "DecodeFrameMap", "generate_heatmaps", "heatmap_mse", "unimodal_mse", "temporal_loss", "pca_loss",
-    "rmse", "require_device", "frames_resize", "frames_augment", "labeled_keypoints", "patch_mask",
+    "rmse", "require_device", "frames_resize", "frames_augment", "labeled_keypoints", "patch_mask", "mv3d_plan", "mv3d_fill", "mv3d_finish",
 ]
 
 
@@ -829,6 +829,76 @@ def labeled_keypoints(keypoints: torch.Tensor, src_hw: torch.Tensor, height: int
     check(_lib.lib().lp_labeled_keypoints(_p(kp), _p(hw), _p(aff), _p(fl), _p(sw), _p(vi), int(uniform_heatmaps), b, k, int(height),
                                           int(width), _p(out), _p(vis), _stream()), "lp_labeled_keypoints")
     return out, vis
+
+
+# --------------------------------------------------------------------------------------------------------
+# multi-view labeled batches with the 3-D augmentation (csrc/mv3d.hip)
+# --------------------------------------------------------------------------------------------------------
+
+MV3D_MAX_VIEWS, MV3D_MAX_KEYPOINTS = 8, 128   # include/lp_hip.h: LP_MV3D_MAX_VIEWS, LP_MV3D_MAX_KEYPOINTS
+
+
+def mv3d_plan(keypoints: torch.Tensor, src_hw: torch.Tensor, bbox: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor,
+              dist: torch.Tensor, draws: torch.Tensor, height: int, width: int, augment: bool = True, shift_param: float = 0.25
+              ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One launch for the batch: labels (B, V, K, 2) in stored-image px -> triangulation, 3-D scale and translation from ``draws`` (B, 4) =
+    [scale, r_x, r_y, r_z], reprojection and the per-view similarity (include/lp_hip.h: lp_mv3d_plan).  Returns ``kp3d`` (B, K, 3), ``kp2d``
+    (B, V, K, 2) in model px, ``affine`` (B, V, 2, 3) stored px -> warped px, ``status`` (B) int32 (0 augmented, 1 not augmented, 2 no label at
+    all, 3 a view with fewer than 3 matched keypoints: not augmented).  Nothing is read back."""
+    require_device(keypoints, src_hw, bbox, intrinsics, extrinsics, dist, draws)
+    b, v, k = _cam_points(keypoints)
+    intr, extr, d12, v2 = _cam_rig(intrinsics, extrinsics, dist, b)
+    if v2 != v:
+        raise ValueError(f"{v} views of keypoints, {v2} cameras")
+    dev = keypoints.device
+    kp, hw, dr = _f32c(keypoints), _f32c(src_hw).to(dev), _f32c(draws).to(dev)
+    bb = _cam_bbox(bbox, b, v, dev)
+    if bb is None or tuple(hw.shape) != (b, v, 2) or tuple(dr.shape) != (b, 4):
+        raise ValueError(f"mv3d_plan: bbox must be {(b, 4 * v)}, src_hw {(b, v, 2)} and draws {(b, 4)}, got "
+                         f"{None if bbox is None else tuple(bbox.shape)}, {tuple(hw.shape)}, {tuple(dr.shape)}")
+    kp3d = torch.empty(b, k, 3, device=dev, dtype=torch.float32)
+    kp2d = torch.empty(b, v, k, 2, device=dev, dtype=torch.float32)
+    affine = torch.empty(b, v, 2, 3, device=dev, dtype=torch.float32)
+    status = torch.empty(b, device=dev, dtype=torch.int32)
+    check(_lib.lib().lp_mv3d_plan(_p(kp), _p(hw), _p(bb), _p(intr), _p(extr), _p(d12), _p(dr), int(bool(augment)), float(shift_param), int(height),
+                                  int(width), b, v, k, _p(kp3d), _p(kp2d), _p(affine), _p(status), _stream()), "lp_mv3d_plan")
+    return kp3d, kp2d, affine, status
+
+
+def _mv3d_images(images_u8: torch.Tensor) -> torch.Tensor:
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise ValueError(f"images must be uint8 (B, H, W, 3), got {images_u8.dtype} {tuple(images_u8.shape)}")
+    return images_u8.contiguous()
+
+
+def mv3d_fill(images_u8: torch.Tensor, mean, std) -> torch.Tensor:
+    """(B, Hs, Ws, 3) uint8 -> (B,) the smallest normalised pixel value of each image (what the reference pads the warped image with)."""
+    require_device(images_u8)
+    src = _mv3d_images(images_u8)
+    b, hs, ws, _ = src.shape
+    fill = torch.empty(b, device=src.device, dtype=torch.float32)
+    check(_lib.lib().lp_mv3d_fill(_p(src), b, hs, ws, C.byref(_frame_norm(mean, std)), _p(fill), _stream()), "lp_mv3d_fill")
+    return fill
+
+
+def mv3d_finish(images_u8: torch.Tensor, affine: torch.Tensor, fill: torch.Tensor, mean, std, view: int, out: torch.Tensor) -> torch.Tensor:
+    """One view's (B, Hs, Ws, 3) uint8 images -> normalise, warp by ``affine[:, view]`` (B, V, 2, 3; stored px -> warped px), resize to
+    ``out``'s (H, W): written straight into ``out[:, view]`` of the fp32 (B, V, 3, H, W) batch (include/lp_hip.h: lp_mv3d_finish)."""
+    require_device(images_u8, affine, fill, out)
+    src = _mv3d_images(images_u8)
+    b, hs, ws, _ = src.shape
+    if out.dim() != 5 or out.dtype != torch.float32 or not out.is_contiguous() or out.shape[0] != b or out.shape[2] != 3:
+        raise ValueError(f"out must be contiguous fp32 ({b}, V, 3, H, W), got {out.dtype} {tuple(out.shape)}")
+    v, h, w = int(out.shape[1]), int(out.shape[3]), int(out.shape[4])
+    if affine.dtype != torch.float32 or not affine.is_contiguous() or tuple(affine.shape) != (b, v, 2, 3):
+        raise ValueError(f"affine must be contiguous fp32 {(b, v, 2, 3)}, got {affine.dtype} {tuple(affine.shape)}")
+    if fill.dtype != torch.float32 or not fill.is_contiguous() or tuple(fill.shape) != (b,):
+        raise ValueError(f"fill must be contiguous fp32 {(b,)}, got {fill.dtype} {tuple(fill.shape)}")
+    if not 0 <= int(view) < v:
+        raise ValueError(f"view {view} outside [0, {v})")
+    check(_lib.lib().lp_mv3d_finish(_p(src), b, hs, ws, _p(affine), _p(fill), C.byref(_frame_norm(mean, std)), v, int(view), h, w, _p(out),
+                                    _stream()), "lp_mv3d_finish")
+    return out
 
 
 # --------------------------------------------------------------------------------------------------------
