@@ -54,6 +54,15 @@ HM_MSE, HM_KL, HM_JS = 0, 1, 2
 # lp_conv_last_kernel() ids 0 .. 9 (include/lp_hip.h: LP_CONV_KERNEL_*; 6 and 7 were conv_spec_kernel's, retired in round 6)
 (CONV_KERNEL_IGEMM, CONV_KERNEL_PIPE, CONV_KERNEL_WGRAD, CONV_KERNEL_WGRAD_PIPE, CONV_KERNEL_PIPE_HALO, CONV_KERNEL_RES2D, _CONV_KERNEL_6,
  _CONV_KERNEL_7, CONV_KERNEL_STEM_WGRAD_NB, CONV_KERNEL_WGRAD_NB) = range(10)
+# a timing label is written for conv_igemm_kernel / conv_wgrad_kernel; when another kernel ran (lp_conv_last_kernel), these (old, new)
+# replacements, applied in order, rename it
+CONV_KERNEL_LABEL = {
+    CONV_KERNEL_PIPE: (("conv_igemm_kernel", "conv_pipe_kernel"),),
+    CONV_KERNEL_PIPE_HALO: (("conv_igemm_kernel", "conv_pipe_kernel"), (">", ",halo>")),
+    CONV_KERNEL_RES2D: (("conv_igemm_kernel<64,", "conv_res2d_kernel<"), ("conv_igemm_kernel<64>", "conv_res2d_kernel<fwd>")),
+    CONV_KERNEL_WGRAD_PIPE: (("conv_wgrad_kernel", "conv_wgrad_pipe_kernel"),),
+    CONV_KERNEL_WGRAD_NB: (("conv_wgrad_kernel", "conv_wgrad_nb_kernel"),),
+}
 BORDER_RENORM, BORDER_CLAMP = 0, 1
 # include/lp_hip.h: LP_AUG_* flags, Philox op numbers, lp_labelaug_local's `which`
 AUG_GEOM, AUG_BLUR, AUG_DROPOUT, AUG_DROP_PER_CHANNEL, AUG_SALT, AUG_PEPPER = 1, 2, 4, 8, 16, 32

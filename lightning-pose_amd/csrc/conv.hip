@@ -1081,66 +1081,52 @@ static void bn_fuse_begin(ConvEpilogue& ep, const lp_bn_fuse* bn) {
 }
 
 // which kernel family the most recent convolution entry point of this thread launched (lp_conv_last_kernel: the bench labels its
-// per-launch timings with the kernel that actually ran; tests assert the path they mean to exercise)
+// per-launch timings with the kernel that actually ran; tests assert the path they mean to exercise).  Assigned by launch_conv() and by
+// the weight-gradient entry points, nowhere else.
 static thread_local int g_last_conv_kernel = LP_CONV_KERNEL_IGEMM;
 
-// Persistent launch of conv_igemm_kernel: at most 2 workgroups per CU (the LDS limit) x 256 CUs, a multiple of 8 so the
-// stride walk keeps every workgroup on its XCD's tile range.  LP_CONV_MAX_WGS overrides the cap (tests use it to force several
-// tiles per workgroup on small problems).
-static int igemm_max_wgs() {
-    if (lp_switches().conv_max_wgs > 0) return lp_switches().conv_max_wgs;
-    static int v = [] {
-        int dev = 0, cus = 0;  // 2 workgroups per CU are resident (LDS-bound): 512 on a full MI355X, fewer on a partition
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        return 2 * cus;
-    }();
-    return v;
-}
+// ---- forward / data-gradient dispatch.  Every forward, inference, Linear / GEMM, data-gradient and stem entry point describes its launch
+// as a ConvProblem; the admits_*() functions say which kernel families the geometry and the store pass admit (shape rules: they read no
+// switch), route_conv() returns the first admitted family the switches allow (switch rules), and launch_conv() maps that ConvRoute to the
+// template instantiation.  A new kernel variant is one shape rule, one line in route_conv() and one case in launch_conv().
+struct ConvRoute {
+    int kernel;   // LP_CONV_KERNEL_IGEMM, _PIPE, _PIPE_HALO or _RES2D (conv_stem2d_kernel reports _RES2D too); kNoKernel = unsupported
+    int bn;       // column block: 64 or 128
+    int mode;     // kMode*: the problem's
+    int ek;       // conv_pipe_kernel's store-pass form (kEk*)
+};
+constexpr int kNoKernel = -1;
 
-// `gemm` (lp_gemm_nt only): operand pitches, batch strides and explicit operand sizes; nz = number of batched GEMMs
-template <int BN, int MODE>
-static int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Lattice& lat, int M, int N, int K, const ConvEpilogue& ep,
-                         hipStream_t st, const GemmExt* gemm = nullptr, int nz = 1, unsigned gemm_x_bytes = 0,
-                         unsigned gemm_w_bytes = 0) {
-    const int tm = (M + kBM - 1) / kBM, tn = (N + BN - 1) / BN, per_z = tm * tn, ntiles = per_z * nz;
-    const int grid = ntiles < igemm_max_wgs() ? ntiles : igemm_max_wgs();
-    const int ck = MODE == kModeDgrad ? g.Co : g.Ci;
-    // byte sizes of the gathered tensor and of the weight matrix (the entry points keep both below 4 GiB)
-    unsigned x_bytes = (unsigned)(2ull * (MODE == kModeDgrad ? (size_t)g.B * g.Ho * g.Wo * g.Co : (size_t)g.B * g.Hi * g.Wi * g.Ci));
-    unsigned w_bytes = (unsigned)(2ull * (size_t)N * (MODE == kModeStem ? (size_t)K : (size_t)g.R * g.S * ck));
-    GemmExt gx{ck, MODE == kModeStem ? K : g.R * g.S * ck, 1, per_z, 0u, 0u, 0u, 0u, 0u, 0u};
-    if (gemm) {
-        gx = *gemm;
-        gx.tiles_per_z = per_z;
-        x_bytes = gemm_x_bytes;
-        w_bytes = gemm_w_bytes;
-    }
-    g_last_conv_kernel = LP_CONV_KERNEL_IGEMM;
-    hipLaunchKernelGGL((conv_igemm_kernel<BN, MODE>), dim3(grid), dim3(256), 0, st, (const unsigned short*)x, (const unsigned short*)w,
-                       x_bytes, w_bytes, g, lat, gx, make_fastdiv(lat.nh * lat.nw), make_fastdiv(lat.nw), M, N, K, tn, ntiles, ep);
-    return grid;
-}
+struct ConvProblem {
+    int mode;               // kModeFwd / kModeDgrad / kModeInfer / kModeStem / kModeAttn: the family of the entry point that asks
+    int ek;                 // the store pass as conv_pipe_kernel knows it (kEk*); -1 = only conv_igemm_kernel implements it
+    const void *x, *w;      // the gathered tensor and the weight matrix
+    ConvGeom g;
+    Lattice lat;
+    int M, N, K;
+    long long seg_rows;     // rows of BatchNorm segment 0 (seg_split_rows); M for a single segment
+    ConvEpilogue ep;
+    // What the entry points do differently, as inputs of route_conv() (everything else about them is in mode / ek / ep):
+    int LpSwitches::*gate;  // the entry point's own A/B switch beside LP_CONV_PIPE: LP_INFER_PIPE (lp_conv_fwd_act), LP_GEMM_PIPE (lp_gemm_nt),
+                            // LP_STEM_2D (the stem); nullptr = none
+    bool dense;             // operands and output without pitch or batch (always, for a convolution): conv_pipe_kernel takes nothing else
+    bool igemm_form;        // conv_igemm_kernel implements the store pass (not the GELU forms: they are conv_pipe_kernel<128> or unsupported)
+    int igemm_cols;         // conv_igemm_kernel's column block follows this count (N; lp_gemm_nt and lp_attn_dscores: the columns STORED),
+                            // conv_pipe_kernel's always follows N
+    // the GEMM entry points (gemm_problem): operand pitches, batch strides and explicit operand sizes of conv_igemm_kernel; nz = batched GEMMs
+    bool gemm;
+    GemmExt gx;
+    int nz;
+    unsigned x_bytes, w_bytes;
+};
 
-// Pipelined kernel (conv_pipe.h): one 512-thread workgroup per CU walks 256 x BN tiles.  LP_CONV_PIPE=0 sends everything to
-// conv_igemm_kernel instead (A/B runs, and the tests that compare the two kernels bit for bit).
-static bool conv_pipe_enabled() { return lp_switches().conv_pipe != 0; }
+static int conv_ck(const ConvProblem& p) { return p.mode == kModeDgrad ? p.g.Co : p.g.Ci; }   // channels of the gathered tensor
 
-static int pipe_max_wgs() {
-    if (lp_switches().conv_max_wgs > 0) return lp_switches().conv_max_wgs;   // (tests: several tiles per workgroup on small problems)
-    static int cus = [] {
-        int dev = 0, c = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 256;
-        return c;
-    }();
-    return cus;
-}
-
-// what the pipelined kernel covers: dense bf16 output of a trunk convolution (no fp32 copy; a bias only in the forward store pass, which
-// the Linear layers of lp_gemm_nt use), K a multiple of 64 and > 0, N a
-// multiple of its column block, fused BatchNorm sums on the atomic path only, and a BatchNorm segment boundary that falls on a 256-row tile
-static bool pipe_eligible(const ConvEpilogue& ep, int M, int N, int K, int ck, long long seg_rows, bool bias_ok = false) {
-    if (!conv_pipe_enabled()) return false;
+// ---- shape rules ----
+// what the pipelined kernel (conv_pipe.h: one 512-thread workgroup per CU walks 256 x BN tiles) covers: dense bf16 output of a trunk
+// convolution (no fp32 copy; a bias only in the forward store pass, which the Linear layers of lp_gemm_nt use), K a multiple of 64 and > 0,
+// N a multiple of its column block, fused BatchNorm sums on the atomic path only, and a BatchNorm segment boundary that falls on a 256-row tile
+static bool pipe_shape_ok(const ConvEpilogue& ep, int M, int N, int K, int ck, long long seg_rows, bool bias_ok) {
     if (ep.out_bf16 == nullptr || ep.out_f32 != nullptr || (ep.bias != nullptr && !bias_ok) || ep.ldo != N || ep.n_store != N) return false;
     if (K <= 0 || ck % kBK != 0 || N % (N > 64 ? 128 : 64) != 0 || M <= 0) return false;
     if (ep.seg_images > 0 && seg_rows % kPM != 0) return false;
@@ -1162,9 +1148,7 @@ static int pipe_dgrad_kind(const ConvEpilogue& ep) {
 
 // HALO form (conv_pipe.h): 3x3 / stride 1 / pad 1 with the tile's input neighbourhood staged once per 64-channel slice.  Eligible when the
 // neighbourhood of every 256-pixel tile (in padded raster coordinates) fits the kernel's halo image: `cap_rows` = 512 (BN = 64) or 384.
-// LP_CONV_HALO=0 keeps those layers on the per-tap ring (A/B runs, bit-identity tests).
-static bool pipe_halo_ok(const ConvGeom& g, int M, int ck, int cap_rows) {
-    if (lp_switches().conv_halo == 0) return false;
+static bool halo_shape_ok(const ConvGeom& g, int M, int ck, int cap_rows) {
     if (g.R != 3 || g.S != 3 || g.stride != 1 || g.pad != 1 || g.Hi != g.Ho || g.Wi != g.Wo || ck % kBK != 0) return false;
     struct Memo { int B, H, W, cap; bool ok; };
     static thread_local Memo memo[8];
@@ -1186,48 +1170,199 @@ static bool pipe_halo_ok(const ConvGeom& g, int M, int ck, int cap_rows) {
 }
 
 // conv_res2d_kernel (conv_res2d.h): 3x3 / stride 1 / pad 1 with 64 channels in and out on 16 x 16 pixel tiles, the whole filter resident
-// in LDS.  LP_CONV_RES2D=0 leaves those layers to conv_pipe_kernel's HALO form (A/B runs, bit-identity tests).
-static bool res2d_ok(const ConvGeom& g, int ck, int N, const ConvEpilogue& ep) {
-    if (lp_switches().conv_res2d == 0) return false;
+// in LDS
+static bool res2d_shape_ok(const ConvGeom& g, int ck, int N) {
     return g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.Hi == g.Ho && g.Wi == g.Wo && ck == 64 && N == 64 && g.Hi % 16 == 0 &&
            g.Wi % 16 == 0;
 }
 
+// conv_stem2d_kernel (conv_res2d.h): the 7x7 / 2 stem on 16 x 16 output tiles, filter resident in LDS
+static bool stem2d_shape_ok(const ConvGeom& g) { return g.Ho % 16 == 0 && g.Wo % 16 == 0 && g.Hi == 2 * g.Ho && g.Wi == 2 * g.Wo; }
+
+// conv_pipe_kernel: a store pass it has, on dense operands; kEkAZB recomputes its output offsets from the row index (full lattice only), the
+// GELU forms exist for the 128-column block only
+static bool admits_pipe(const ConvProblem& p) {
+    if (p.ek < 0 || !p.dense) return false;
+    if (p.ek == kEkAZB && !(p.lat.hstep == 1 && p.lat.wstep == 1)) return false;
+    if ((p.ek == kEkGeluFwd || p.ek == kEkGeluBwd) && p.N % 128 != 0) return false;
+    return pipe_shape_ok(p.ep, p.M, p.N, p.K, conv_ck(p), p.seg_rows, p.mode != kModeDgrad);
+}
+
+// ... its HALO form: the store passes of the trunk's 3x3 layers (forward, inference, the data gradient that recomputes its mask from z)
+static bool admits_halo(const ConvProblem& p) {
+    return (p.ek == kEkNone || p.ek == kEkInfer || p.ek == kEkZ) && halo_shape_ok(p.g, p.M, conv_ck(p), p.N > 64 ? 384 : 512);
+}
+
+// conv_res2d_kernel: whatever conv_pipe_kernel would take of layer1's 3x3 layers, with the store passes kEkNone and kEkZ and no bias.  Its
+// inference store pass (lp_conv_fwd_act) is the exception twice over: it adds the bias but no residual, and it asks for the shape alone
+// (whatever has that shape there passes pipe_shape_ok as well).
+static bool admits_res2d(const ConvProblem& p) {
+    if (!res2d_shape_ok(p.g, conv_ck(p), p.N)) return false;
+    if (p.mode == kModeInfer) return p.ep.addend == nullptr;
+    return (p.ek == kEkNone || p.ek == kEkZ) && p.ep.bias == nullptr && admits_pipe(p);
+}
+
+// ---- switch rules ----
+// The first family, best first, that the problem admits and the switches allow; conv_igemm_kernel closes every list but the GELU forms'.
+// LP_CONV_PIPE=0 sends everything to conv_igemm_kernel (A/B runs, and the tests that compare the kernels bit for bit), and so does the
+// entry point's own switch (ConvProblem::gate) when it is 0; LP_CONV_RES2D=0 leaves layer1's 3x3 layers to conv_pipe_kernel's HALO form,
+// LP_CONV_HALO=0 keeps the 3x3 layers on its per-tap ring.  A shape rule is asked only once the switches let its family run, so
+// halo_shape_ok's memo sees the geometries that can take the HALO form and no others.
+static ConvRoute route_conv(const ConvProblem& p, const LpSwitches& sw) {
+    const bool pipe = sw.conv_pipe != 0 && (p.gate == nullptr || sw.*p.gate != 0);
+    if (p.mode == kModeStem) return ConvRoute{pipe && stem2d_shape_ok(p.g) ? LP_CONV_KERNEL_RES2D : LP_CONV_KERNEL_IGEMM, 64, p.mode, p.ek};
+    if (pipe && sw.conv_res2d != 0 && admits_res2d(p)) return ConvRoute{LP_CONV_KERNEL_RES2D, 64, p.mode, p.ek};
+    if (pipe && admits_pipe(p))
+        return ConvRoute{sw.conv_halo != 0 && admits_halo(p) ? LP_CONV_KERNEL_PIPE_HALO : LP_CONV_KERNEL_PIPE, p.N > 64 ? 128 : 64, p.mode, p.ek};
+    return ConvRoute{p.igemm_form ? LP_CONV_KERNEL_IGEMM : kNoKernel, p.igemm_cols > 64 ? 128 : 64, p.mode, p.ek};
+}
+
+// ---- launch ----
+// Workgroups of a persistent launch: `per_cu` per CU - 2 for conv_igemm_kernel (the LDS limit; 512 on a full MI355X, fewer on a partition:
+// a multiple of 8, so the stride walk keeps every workgroup on its XCD's tile range), 1 for the 512-thread kernels (conv_pipe_kernel,
+// conv_res2d_kernel; conv_stem2d_kernel takes twice that).  LP_CONV_MAX_WGS overrides the product (tests use it to force several tiles per
+// workgroup on small problems).
+static int conv_max_wgs(int per_cu) {
+    if (lp_switches().conv_max_wgs > 0) return lp_switches().conv_max_wgs;
+    static int cus = [] {
+        int dev = 0, c = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 256;
+        return c;
+    }();
+    return per_cu * cus;
+}
+
+template <int BN, int MODE>
+static void launch_igemm(const ConvProblem& p, hipStream_t st) {
+    const ConvGeom& g = p.g;
+    const int tm = (p.M + kBM - 1) / kBM, tn = (p.N + BN - 1) / BN, per_z = tm * tn, ntiles = per_z * p.nz;
+    const int grid = ntiles < conv_max_wgs(2) ? ntiles : conv_max_wgs(2);
+    const int ck = MODE == kModeDgrad ? g.Co : g.Ci;
+    // byte sizes of the gathered tensor and of the weight matrix (the entry points keep both below 4 GiB)
+    unsigned x_bytes = (unsigned)(2ull * (MODE == kModeDgrad ? (size_t)g.B * g.Ho * g.Wo * g.Co : (size_t)g.B * g.Hi * g.Wi * g.Ci));
+    unsigned w_bytes = (unsigned)(2ull * (size_t)p.N * (MODE == kModeStem ? (size_t)p.K : (size_t)g.R * g.S * ck));
+    GemmExt gx{ck, MODE == kModeStem ? p.K : g.R * g.S * ck, 1, per_z, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (p.gemm) {
+        gx = p.gx;
+        gx.tiles_per_z = per_z;
+        x_bytes = p.x_bytes;
+        w_bytes = p.w_bytes;
+    }
+    hipLaunchKernelGGL((conv_igemm_kernel<BN, MODE>), dim3(grid), dim3(256), 0, st, (const unsigned short*)p.x, (const unsigned short*)p.w,
+                       x_bytes, w_bytes, g, p.lat, gx, make_fastdiv(p.lat.nh * p.lat.nw), make_fastdiv(p.lat.nw), p.M, p.N, p.K, tn, ntiles, p.ep);
+}
+
 template <int MODE, bool INFER = false>
-static int launch_res2d(const void* x, const void* w, const ConvGeom& g, const ConvEpilogue& ep, hipStream_t st) {
+static void launch_res2d(const ConvProblem& p, hipStream_t st) {
+    const ConvGeom& g = p.g;
     const int ntiles = g.B * (g.Hi / 16) * (g.Wi / 16);
-    const int grid = ntiles < pipe_max_wgs() ? ntiles : pipe_max_wgs();
+    const int grid = ntiles < conv_max_wgs(1) ? ntiles : conv_max_wgs(1);
     const unsigned x_bytes = (unsigned)(2ull * g.B * g.Hi * g.Wi * 64), w_bytes = (unsigned)(2ull * 64 * 9 * 64);
-    g_last_conv_kernel = LP_CONV_KERNEL_RES2D;
-    hipLaunchKernelGGL((conv_res2d_kernel<MODE, INFER>), dim3(grid), dim3(512), 0, st, (const unsigned short*)x, (const unsigned short*)w, x_bytes, w_bytes,
-                       g.B, g.Hi, g.Wi, ntiles, ep);
-    return grid;
+    hipLaunchKernelGGL((conv_res2d_kernel<MODE, INFER>), dim3(grid), dim3(512), 0, st, (const unsigned short*)p.x, (const unsigned short*)p.w, x_bytes,
+                       w_bytes, g.B, g.Hi, g.Wi, ntiles, p.ep);
+}
+
+static void launch_stem2d(const ConvProblem& p, hipStream_t st) {
+    const ConvGeom& g = p.g;
+    const int ntiles = g.B * (g.Ho / 16) * (g.Wo / 16);
+    const int grid = ntiles < 2 * conv_max_wgs(1) ? ntiles : 2 * conv_max_wgs(1);
+    hipLaunchKernelGGL(conv_stem2d_kernel, dim3(grid), dim3(512), 0, st, (const unsigned short*)p.x, (const unsigned short*)p.w,
+                       (unsigned)(2ull * g.B * g.Hi * g.Wi * 4), g.B, g.Ho, g.Wo, ntiles, p.ep);
 }
 
 template <int BN, int MODE, int EK, bool HALO = false>
-static int launch_pipe(const void* x, const void* w, const ConvGeom& g, const Lattice& lat, int M, int N, int K, const ConvEpilogue& ep,
-                        hipStream_t st) {
-    const int tm = (M + kPM - 1) / kPM, tn = N / BN, ntiles = tm * tn;
-    const int grid = ntiles < pipe_max_wgs() ? ntiles : pipe_max_wgs();
+static void launch_pipe(const ConvProblem& p, hipStream_t st) {
+    const ConvGeom& g = p.g;
+    const int tm = (p.M + kPM - 1) / kPM, tn = p.N / BN, ntiles = tm * tn;
+    const int grid = ntiles < conv_max_wgs(1) ? ntiles : conv_max_wgs(1);
     const int ck = MODE == kModeDgrad ? g.Co : g.Ci;
     const unsigned x_bytes = (unsigned)(2ull * (MODE == kModeDgrad ? (size_t)g.B * g.Ho * g.Wo * g.Co : (size_t)g.B * g.Hi * g.Wi * g.Ci));
-    const unsigned w_bytes = (unsigned)(2ull * (size_t)N * g.R * g.S * ck);
-    g_last_conv_kernel = HALO ? LP_CONV_KERNEL_PIPE_HALO : LP_CONV_KERNEL_PIPE;
+    const unsigned w_bytes = (unsigned)(2ull * (size_t)p.N * g.R * g.S * ck);
     const HaloDivs hd{make_fastdiv(g.Hi), make_fastdiv(g.Wi + 2), make_fastdiv(g.Hi + 2)};
-    hipLaunchKernelGGL((conv_pipe_kernel<BN, MODE, EK, HALO>), dim3(grid), dim3(512), 0, st, (const unsigned short*)x, (const unsigned short*)w,
-                       x_bytes, w_bytes, g, lat, make_fastdiv(lat.nh * lat.nw), make_fastdiv(lat.nw), M, N, K, tn, ntiles, ep, hd);
-    return grid;
+    hipLaunchKernelGGL((conv_pipe_kernel<BN, MODE, EK, HALO>), dim3(grid), dim3(512), 0, st, (const unsigned short*)p.x, (const unsigned short*)p.w,
+                       x_bytes, w_bytes, g, p.lat, make_fastdiv(p.lat.nh * p.lat.nw), make_fastdiv(p.lat.nw), p.M, p.N, p.K, tn, ntiles, p.ep, hd);
 }
 
+// the instantiations that exist for both column blocks
 template <int BN>
-static int launch_pipe_dgrad(int kind, const void* x, const void* w, const ConvGeom& g, const Lattice& lat, int M, int N, int K,
-                             const ConvEpilogue& ep, hipStream_t st) {
-    if (kind == kEkZ && BN == 64 && ep.bias == nullptr && res2d_ok(g, g.Co, N, ep)) return launch_res2d<kModeDgrad>(x, w, g, ep, st);
-    if (kind == kEkZ && pipe_halo_ok(g, M, g.Co, BN == 64 ? 512 : 384)) return launch_pipe<BN, kModeDgrad, kEkZ, true>(x, w, g, lat, M, N, K, ep, st);
-    if (kind == kEkZ) return launch_pipe<BN, kModeDgrad, kEkZ>(x, w, g, lat, M, N, K, ep, st);
-    if (kind == kEkAZB) return launch_pipe<BN, kModeDgrad, kEkAZB>(x, w, g, lat, M, N, K, ep, st);
-    if (kind == kEkPB) return launch_pipe<BN, kModeDgrad, kEkPB>(x, w, g, lat, M, N, K, ep, st);
-    return launch_pipe<BN, kModeDgrad, kEkPlain>(x, w, g, lat, M, N, K, ep, st);
+static void launch_conv_bn(const ConvRoute& r, const ConvProblem& p, hipStream_t st) {
+    if (r.kernel == LP_CONV_KERNEL_IGEMM) {
+        switch (r.mode) {
+            case kModeFwd: return launch_igemm<BN, kModeFwd>(p, st);
+            case kModeDgrad: return launch_igemm<BN, kModeDgrad>(p, st);
+            case kModeInfer: return launch_igemm<BN, kModeInfer>(p, st);
+            default: return launch_igemm<BN, kModeAttn>(p, st);
+        }
+    }
+    const bool halo = r.kernel == LP_CONV_KERNEL_PIPE_HALO;   // (route_conv: kEkNone, kEkInfer and kEkZ only)
+    switch (r.ek) {
+        case kEkNone: return halo ? launch_pipe<BN, kModeFwd, kEkNone, true>(p, st) : launch_pipe<BN, kModeFwd, kEkNone>(p, st);
+        case kEkInfer: return halo ? launch_pipe<BN, kModeFwd, kEkInfer, true>(p, st) : launch_pipe<BN, kModeFwd, kEkInfer>(p, st);
+        case kEkZ: return halo ? launch_pipe<BN, kModeDgrad, kEkZ, true>(p, st) : launch_pipe<BN, kModeDgrad, kEkZ>(p, st);
+        case kEkAZB: return launch_pipe<BN, kModeDgrad, kEkAZB>(p, st);
+        case kEkPB: return launch_pipe<BN, kModeDgrad, kEkPB>(p, st);
+        default: return launch_pipe<BN, kModeDgrad, kEkPlain>(p, st);
+    }
+}
+
+// A route's template instantiation - every one that exists is named here or in launch_conv_bn, and nowhere else - and the one place that
+// records the kernel family for lp_conv_last_kernel.  What route_conv() cannot return (a GELU form at 64 columns, the stem at 128, a HALO
+// form of kEkAZB, ...) has no instantiation.
+static void launch_conv(const ConvRoute& r, const ConvProblem& p, hipStream_t st) {
+    g_last_conv_kernel = r.kernel;
+    if (r.kernel == LP_CONV_KERNEL_RES2D) {
+        switch (r.mode) {
+            case kModeStem: return launch_stem2d(p, st);
+            case kModeInfer: return launch_res2d<kModeFwd, true>(p, st);
+            case kModeDgrad: return launch_res2d<kModeDgrad>(p, st);
+            default: return launch_res2d<kModeFwd>(p, st);
+        }
+    }
+    if (r.mode == kModeStem) return launch_igemm<64, kModeStem>(p, st);
+    if (r.ek == kEkGeluFwd) return launch_pipe<128, kModeFwd, kEkGeluFwd>(p, st);
+    if (r.ek == kEkGeluBwd) return launch_pipe<128, kModeFwd, kEkGeluBwd>(p, st);
+    if (r.bn == 128) launch_conv_bn<128>(r, p, st);
+    else launch_conv_bn<64>(r, p, st);
+}
+
+// route, then launch: what every entry point with one launch ends on
+static int run_conv(const ConvProblem& p, lp_stream_t stream) {
+    const ConvRoute r = route_conv(p, lp_switches());
+    if (r.kernel == kNoKernel) return LP_ERR_UNSUPPORTED;
+    launch_conv(r, p, (hipStream_t)stream);
+    return launch_status();
+}
+
+// a convolution entry point's problem on the full lattices; the caller fills in the store pass (ep, ek) and its switch (gate)
+static ConvProblem conv_problem(int mode, const void* x, const void* w, const ConvGeom& g, int rows_h, int rows_w, int N, int K) {
+    ConvProblem p{};
+    p.mode = mode, p.ek = -1, p.x = x, p.w = w, p.g = g;
+    p.lat = Lattice{0, 1, rows_h, 0, 1, rows_w, 0, 1, g.R, 0, 1, g.S};
+    p.M = g.B * rows_h * rows_w, p.N = N, p.K = K, p.seg_rows = p.M;
+    p.dense = true, p.igemm_form = true, p.igemm_cols = N, p.nz = 1;
+    return p;
+}
+
+// The problem of the GEMM entry points (lp_gemm_nt, its GELU forms, lp_attn_dscores): C[z] = A[z] B[z]^T as a 1x1 convolution over M "pixels"
+// of K channels on the unit lattice, with the operand pitches, batch strides and sizes conv_igemm_kernel needs when they are not the dense
+// ones.  `c_align`: what the output's pitch and batch strides must be a multiple of (8 where the store pass reads a tensor at the output's
+// offsets in 16-B chunks).  Returns LP_OK or the code of the first check that fails; the caller fills in the store pass.
+static int gemm_problem(ConvProblem& p, int mode, const void* a, int lda, const void* b, int ldb, int ldc, int c_align, int M, int N, int K,
+                        const lp_gemm_batch* batch) {
+    if (K % kBK != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % c_align != 0) return LP_ERR_UNSUPPORTED;
+    const lp_gemm_batch z = batch ? *batch : lp_gemm_batch{1, 1, 0, 0, 0, 0, 0, 0};
+    LP_REQUIRE(z.nb > 0 && z.nh > 0 && z.a_b >= 0 && z.a_h >= 0 && z.b_b >= 0 && z.b_h >= 0 && z.c_b >= 0 && z.c_h >= 0);
+    const long long a_elems = (z.nb - 1) * z.a_b + (z.nh - 1) * z.a_h + (long long)(M - 1) * lda + K;
+    const long long b_elems = (z.nb - 1) * z.b_b + (z.nh - 1) * z.b_h + (long long)(N - 1) * ldb + K;
+    const long long c_elems = (z.nb - 1) * z.c_b + (z.nh - 1) * z.c_h + (long long)M * ldc;
+    if (a_elems >= (1LL << 31) || b_elems >= (1LL << 31) || c_elems >= (1LL << 32)) return LP_ERR_UNSUPPORTED;
+    if ((z.a_b | z.a_h | z.b_b | z.b_h) % 8 != 0 || (z.c_b | z.c_h) % c_align != 0) return LP_ERR_UNSUPPORTED;  // 16-B operand chunks
+    p = conv_problem(mode, a, b, ConvGeom{1, 1, M, K, 1, M, N, 1, 1, 1, 0}, 1, M, N, K);
+    p.dense = z.nb * z.nh == 1 && lda == K && ldb == K && ldc == N;
+    p.gemm = true, p.nz = z.nb * z.nh, p.x_bytes = (unsigned)(2 * a_elems), p.w_bytes = (unsigned)(2 * b_elems);
+    p.gx = GemmExt{lda, ldb, z.nh, 0, (unsigned)(2 * z.a_b), (unsigned)(2 * z.a_h), (unsigned)(2 * z.b_b), (unsigned)(2 * z.b_h), (unsigned)z.c_b,
+                   (unsigned)z.c_h};
+    return LP_OK;
 }
 
 }  // namespace lp
@@ -1312,7 +1447,7 @@ static WgradRoute plan_wgrad_pipe(const ConvGeom& g, int split_hint) {
     // the 64-B request granularity its LDS swizzle forces on the loads (measured per layer, profiles/archive/r03g_layer_table.txt)
     p.tuned = (long long)p.tiles_a * 256 * 8 <= (long long)p.Ka * 9 && (long long)p.Ka * p.Cb >= 120LL * (p.Ka + p.Cb);
     const int tiles = p.tiles_a * p.tiles_b;
-    const int cus = pipe_max_wgs();
+    const int cus = conv_max_wgs(1);
     const int ksteps = (M + kBK - 1) / kBK;
     int split = split_hint;
     if (split <= 0) {
@@ -1353,7 +1488,7 @@ static WgradRoute plan_wgrad_nb(const ConvGeom& g, int split_hint) {
     if (split <= 0) {
         // in microseconds at the MFMA rate: a K step is 9 x 4 x bn/16 MFMAs per CU; a workgroup's partial tile (295 KB for either bn) takes
         // ~15 us to leave at a 1/256 share of the memory rate, and the reduction reads it back
-        const int cus = pipe_max_wgs();
+        const int cus = conv_max_wgs(1);
         const double step_us = 0.96 * p.bn / 128.0;
         double best = 1e30;
         for (int s = 1; s <= ksteps && s * tiles <= 2 * cus; ++s) {
@@ -1475,33 +1610,17 @@ static int conv_fwd_impl(const void* x, const void* w, const lp_conv_geom* geom,
     if (g.Ci % kBK != 0 || g.R * g.S > 32 || (long long)g.B * g.Hi * g.Wi * g.Ci >= (1LL << 31) ||
         (long long)g.B * g.Ho * g.Wo * ldo >= (1LL << 32))
         return LP_ERR_UNSUPPORTED;
-    const int M = g.B * g.Ho * g.Wo, N = g.Co, K = g.R * g.S * g.Ci;
-    ConvEpilogue ep{(unsigned short*)out_bf16, out_f32, ldo, n_store > 0 ? n_store : N, bias};
-    long long split = M;
+    ConvProblem p = conv_problem(kModeFwd, x, w, g, g.Ho, g.Wo, g.Co, g.R * g.S * g.Ci);
+    p.ek = kEkNone;
+    p.ep = ConvEpilogue{(unsigned short*)out_bf16, out_f32, ldo, n_store > 0 ? n_store : p.N, bias};
     if (bn) {
         LP_REQUIRE(bn->sums && bn->seg_images >= 0);
-        if (N % 8 != 0) return LP_ERR_UNSUPPORTED;
-        split = seg_split_rows(bn->seg_images, g.B, (long long)g.Ho * g.Wo, M);
-        if (split < 0) return LP_ERR_UNSUPPORTED;
-        bn_fuse_begin(ep, bn);
+        if (p.N % 8 != 0) return LP_ERR_UNSUPPORTED;
+        p.seg_rows = seg_split_rows(bn->seg_images, g.B, (long long)g.Ho * g.Wo, p.M);
+        if (p.seg_rows < 0) return LP_ERR_UNSUPPORTED;
+        bn_fuse_begin(p.ep, bn);
     }
-    hipStream_t st = (hipStream_t)stream;
-    const Lattice lat{0, 1, g.Ho, 0, 1, g.Wo, 0, 1, g.R, 0, 1, g.S};
-    if (pipe_eligible(ep, M, N, K, g.Ci, split, true)) {
-        if (N > 64) {
-            const bool halo = pipe_halo_ok(g, M, g.Ci, 384);
-            if (halo) launch_pipe<128, kModeFwd, kEkNone, true>(x, w, g, lat, M, N, K, ep, st);
-            else launch_pipe<128, kModeFwd, kEkNone>(x, w, g, lat, M, N, K, ep, st);
-        } else if (ep.bias == nullptr && res2d_ok(g, g.Ci, N, ep)) {
-            launch_res2d<kModeFwd>(x, w, g, ep, st);
-        } else if (pipe_halo_ok(g, M, g.Ci, 512)) {
-            launch_pipe<64, kModeFwd, kEkNone, true>(x, w, g, lat, M, N, K, ep, st);
-        } else {
-            launch_pipe<64, kModeFwd, kEkNone>(x, w, g, lat, M, N, K, ep, st);
-        }
-    } else if (N > 64) launch_igemm<128, kModeFwd>(x, w, g, lat, M, N, K, ep, st);
-    else launch_igemm<64, kModeFwd>(x, w, g, lat, M, N, K, ep, st);
-    return launch_status();
+    return run_conv(p, stream);
 }
 
 extern "C" int lp_conv_last_kernel(void) { return lp::g_last_conv_kernel; }
@@ -1512,7 +1631,9 @@ extern "C" int lp_conv_fwd(const void* x, const void* w, const lp_conv_geom* geo
 }
 
 // out = [relu](conv(x, w) + bias + residual): the inference form of conv -> BatchNorm [-> + identity] [-> ReLU] once the BatchNorm
-// (running statistics) is folded into w and bias (lp_bn_fold)
+// (running statistics) is folded into w and bias (lp_bn_fold).  The pipelined forward kernels with the residual and the ReLU in their store
+// pass (round 4: the inference store pass of conv_res2d_kernel for layer1's 64 -> 64 3x3 layers); LP_INFER_PIPE=0: A/B runs keep
+// conv_igemm_kernel<infer>
 extern "C" int lp_conv_fwd_act(const void* x, const void* w, const lp_conv_geom* geom, const float* bias, const void* residual_bf16, int relu,
                                void* out_bf16, lp_stream_t stream) {
     using namespace lp;
@@ -1521,34 +1642,11 @@ extern "C" int lp_conv_fwd_act(const void* x, const void* w, const lp_conv_geom*
     if (g.Ci % kBK != 0 || g.Co % 8 != 0 || g.R * g.S > 32 || (long long)g.B * g.Hi * g.Wi * g.Ci >= (1LL << 31) ||
         (long long)g.B * g.Ho * g.Wo * g.Co >= (1LL << 32))
         return LP_ERR_UNSUPPORTED;
-    const int M = g.B * g.Ho * g.Wo, N = g.Co, K = g.R * g.S * g.Ci;
-    ConvEpilogue ep{};
-    ep.out_bf16 = (unsigned short*)out_bf16, ep.ldo = N, ep.n_store = N, ep.bias = bias;
-    ep.addend = (const unsigned short*)residual_bf16, ep.relu_fwd = relu != 0;
-    const Lattice lat{0, 1, g.Ho, 0, 1, g.Wo, 0, 1, g.R, 0, 1, g.S};
-    hipStream_t st = (hipStream_t)stream;
-    // the pipelined forward kernel with the residual and the ReLU in its store pass (LP_INFER_PIPE=0: A/B runs keep conv_igemm_kernel<infer>)
-    const bool ip = lp_switches().infer_pipe != 0;
-    if (ip && conv_pipe_enabled() && ep.addend == nullptr && res2d_ok(g, g.Ci, N, ep)) {   // (LP_CONV_PIPE=0 keeps these layers on conv_igemm_kernel too)
-        // layer1's 64 -> 64 3x3 layers: 16 x 16 tiles, the filter resident in LDS (round 4: the inference store pass of conv_res2d_kernel)
-        launch_res2d<kModeFwd, true>(x, w, g, ep, st);
-        return launch_status();
-    }
-    if (ip && pipe_eligible(ep, M, N, K, g.Ci, M, true)) {
-        if (N > 64) {
-            if (pipe_halo_ok(g, M, g.Ci, 384)) launch_pipe<128, kModeFwd, kEkInfer, true>(x, w, g, lat, M, N, K, ep, st);
-            else launch_pipe<128, kModeFwd, kEkInfer>(x, w, g, lat, M, N, K, ep, st);
-        } else if (pipe_halo_ok(g, M, g.Ci, 512)) {
-            launch_pipe<64, kModeFwd, kEkInfer, true>(x, w, g, lat, M, N, K, ep, st);
-        } else {
-            launch_pipe<64, kModeFwd, kEkInfer>(x, w, g, lat, M, N, K, ep, st);
-        }
-        return launch_status();
-    }
-    g_last_conv_kernel = LP_CONV_KERNEL_IGEMM;
-    if (N > 64) launch_igemm<128, kModeInfer>(x, w, g, lat, M, N, K, ep, st);
-    else launch_igemm<64, kModeInfer>(x, w, g, lat, M, N, K, ep, st);
-    return launch_status();
+    ConvProblem p = conv_problem(kModeInfer, x, w, g, g.Ho, g.Wo, g.Co, g.R * g.S * g.Ci);
+    p.ek = kEkInfer, p.gate = &LpSwitches::infer_pipe;
+    p.ep.out_bf16 = (unsigned short*)out_bf16, p.ep.ldo = p.N, p.ep.n_store = p.N, p.ep.bias = bias;
+    p.ep.addend = (const unsigned short*)residual_bf16, p.ep.relu_fwd = relu != 0;
+    return run_conv(p, stream);
 }
 
 // conv + the [sum, sum of squares] of its (bf16-rounded) output per channel: the statistics pass of the BatchNorm that follows
@@ -1558,39 +1656,19 @@ extern "C" int lp_conv_fwd_bn(const void* x, const void* w, const lp_conv_geom* 
     return conv_fwd_impl(x, w, geom, nullptr, out_bf16, nullptr, geom->Co, 0, bn, stream);
 }
 
-// C[z][m][n] = sum_k A[z][m][k] * B[z][n][k] (+ bias[n]): the forward kernel as a plain (batched, strided) NT GEMM
+// C[z][m][n] = sum_k A[z][m][k] * B[z][n][k] (+ bias[n]): the forward kernel as a plain (batched, strided) NT GEMM.  A dense, unbatched
+// product (every Linear layer of the ViT, forward and data gradient) is a 1x1 convolution: the pipelined kernel (LP_GEMM_PIPE=0, A/B: keeps
+// the Linear layers on conv_igemm_kernel)
 extern "C" int lp_gemm_nt(const void* a, int lda, const void* b, int ldb, void* c_bf16, float* c_f32, int ldc, int M, int N, int K,
                           int n_store, const float* bias, const lp_gemm_batch* batch, lp_stream_t stream) {
     using namespace lp;
     LP_REQUIRE(a && b && (c_bf16 || c_f32) && M > 0 && N > 0 && K > 0 && lda >= K && ldb >= K && ldc > 0);
-    if (K % kBK != 0 || lda % 8 != 0 || ldb % 8 != 0) return LP_ERR_UNSUPPORTED;
-    const int nb = batch ? batch->nb : 1, nh = batch ? batch->nh : 1;
-    LP_REQUIRE(nb > 0 && nh > 0);
-    const long long a_b = batch ? batch->a_b : 0, a_h = batch ? batch->a_h : 0, b_b = batch ? batch->b_b : 0, b_h = batch ? batch->b_h : 0;
-    const long long c_b = batch ? batch->c_b : 0, c_h = batch ? batch->c_h : 0;
-    LP_REQUIRE(a_b >= 0 && a_h >= 0 && b_b >= 0 && b_h >= 0 && c_b >= 0 && c_h >= 0);
-    const long long a_elems = (nb - 1) * a_b + (nh - 1) * a_h + (long long)(M - 1) * lda + K;
-    const long long b_elems = (nb - 1) * b_b + (nh - 1) * b_h + (long long)(N - 1) * ldb + K;
-    const long long c_elems = (nb - 1) * c_b + (nh - 1) * c_h + (long long)M * ldc;
-    if (a_elems >= (1LL << 31) || b_elems >= (1LL << 31) || c_elems >= (1LL << 32)) return LP_ERR_UNSUPPORTED;
-    if ((a_b | a_h | b_b | b_h) % 8 != 0) return LP_ERR_UNSUPPORTED;  // 16-B operand chunks
-    ConvGeom g{1, 1, M, K, 1, M, N, 1, 1, 1, 0};
-    ConvEpilogue ep{(unsigned short*)c_bf16, c_f32, ldc, n_store > 0 ? n_store : N, bias};
-    GemmExt gx{lda, ldb, nh, 0, (unsigned)(2 * a_b), (unsigned)(2 * a_h), (unsigned)(2 * b_b), (unsigned)(2 * b_h), (unsigned)c_b,
-               (unsigned)c_h};
-    const Lattice lat{0, 1, 1, 0, 1, M, 0, 1, 1, 0, 1, 1};
-    hipStream_t st = (hipStream_t)stream;
-    const int nstore = ep.n_store;
-    // a dense, unbatched product (every Linear layer of the ViT, forward and data gradient) is a 1x1 convolution: the pipelined kernel
-    // (LP_GEMM_PIPE=0, A/B: keeps the Linear layers on conv_igemm_kernel)
-    if (lp_switches().gemm_pipe != 0 && nb * nh == 1 && lda == K && ldb == K && ldc == N && pipe_eligible(ep, M, N, K, K, M, true)) {
-        if (N > 64) launch_pipe<128, kModeFwd, kEkNone>(a, b, g, lat, M, N, K, ep, st);
-        else launch_pipe<64, kModeFwd, kEkNone>(a, b, g, lat, M, N, K, ep, st);
-        return launch_status();
-    }
-    if (nstore > 64) launch_igemm<128, kModeFwd>(a, b, g, lat, M, N, K, ep, st, &gx, nb * nh, (unsigned)(2 * a_elems), (unsigned)(2 * b_elems));
-    else launch_igemm<64, kModeFwd>(a, b, g, lat, M, N, K, ep, st, &gx, nb * nh, (unsigned)(2 * a_elems), (unsigned)(2 * b_elems));
-    return launch_status();
+    ConvProblem p;
+    if (const int rc = gemm_problem(p, kModeFwd, a, lda, b, ldb, ldc, 1, M, N, K, batch)) return rc;
+    p.ek = kEkNone, p.gate = &LpSwitches::gemm_pipe;
+    p.ep = ConvEpilogue{(unsigned short*)c_bf16, c_f32, ldc, n_store > 0 ? n_store : N, bias};
+    p.igemm_cols = p.ep.n_store;
+    return run_conv(p, stream);
 }
 
 // lp_gemm_nt (+ bias) that also writes GELU of its output (conv_pipe.h: kEkGeluFwd)
@@ -1598,14 +1676,12 @@ extern "C" int lp_gemm_nt_gelu_fwd(const void* a, const void* b, const float* bi
                                    lp_stream_t stream) {
     using namespace lp;
     LP_REQUIRE(a && b && c_bf16 && act_bf16 && M > 0 && N > 0 && K > 0);
-    if ((long long)M * K >= (1LL << 31) || (long long)N * K >= (1LL << 31) || (long long)M * N >= (1LL << 32)) return LP_ERR_UNSUPPORTED;
-    ConvGeom g{1, 1, M, K, 1, M, N, 1, 1, 1, 0};
-    ConvEpilogue ep{(unsigned short*)c_bf16, nullptr, N, N, bias};
-    ep.out2_bf16 = (unsigned short*)act_bf16;
-    const Lattice lat{0, 1, 1, 0, 1, M, 0, 1, 1, 0, 1, 1};
-    if (N % 128 != 0 || !pipe_eligible(ep, M, N, K, K, M, true)) return LP_ERR_UNSUPPORTED;
-    launch_pipe<128, kModeFwd, kEkGeluFwd>(a, b, g, lat, M, N, K, ep, (hipStream_t)stream);
-    return launch_status();
+    ConvProblem p;
+    if (const int rc = gemm_problem(p, kModeFwd, a, K, b, K, N, 1, M, N, K, nullptr)) return rc;
+    p.ek = kEkGeluFwd, p.igemm_form = false;
+    p.ep = ConvEpilogue{(unsigned short*)c_bf16, nullptr, N, N, bias};
+    p.ep.out2_bf16 = (unsigned short*)act_bf16;
+    return run_conv(p, stream);
 }
 
 // lp_gemm_nt with GELU's backward in the store pass (conv_pipe.h: kEkGeluBwd)
@@ -1613,15 +1689,13 @@ extern "C" int lp_gemm_nt_gelu_bwd(const void* a, const void* b, const void* u_b
                                    lp_stream_t stream) {
     using namespace lp;
     LP_REQUIRE(a && b && u_bf16 && c_bf16 && M > 0 && N > 0 && K > 0);
-    if ((long long)M * K >= (1LL << 31) || (long long)N * K >= (1LL << 31) || (long long)M * N >= (1LL << 32)) return LP_ERR_UNSUPPORTED;
-    ConvGeom g{1, 1, M, K, 1, M, N, 1, 1, 1, 0};
-    ConvEpilogue ep{(unsigned short*)c_bf16, nullptr, N, N, nullptr};
-    ep.addend = (const unsigned short*)u_bf16;
-    ep.stats_sums = colsum;
-    const Lattice lat{0, 1, 1, 0, 1, M, 0, 1, 1, 0, 1, 1};
-    if (N % 128 != 0 || !pipe_eligible(ep, M, N, K, K, M)) return LP_ERR_UNSUPPORTED;
-    launch_pipe<128, kModeFwd, kEkGeluBwd>(a, b, g, lat, M, N, K, ep, (hipStream_t)stream);
-    return launch_status();
+    ConvProblem p;
+    if (const int rc = gemm_problem(p, kModeFwd, a, K, b, K, N, 1, M, N, K, nullptr)) return rc;
+    p.ek = kEkGeluBwd, p.igemm_form = false;
+    p.ep = ConvEpilogue{(unsigned short*)c_bf16, nullptr, N, N, nullptr};
+    p.ep.addend = (const unsigned short*)u_bf16;
+    p.ep.stats_sums = colsum;
+    return run_conv(p, stream);
 }
 
 // Attention backward, score gradient: dS[z] = scale * P[z] o (dO[z] V[z]^T - D[z] 1^T), D = rowsum(dO o O) (lp_attn_rowdot).  The
@@ -1632,30 +1706,19 @@ extern "C" int lp_attn_dscores(const void* d_out, int ld_do, const void* v, int 
     using namespace lp;
     LP_REQUIRE(d_out && v && p_bf16 && d_rows && ds_bf16 && batch && M > 0 && N > 0 && K > 0 && ld_do >= K && ldv >= K && ldc >= N &&
                d_row_stride > 0 && d_b >= 0 && d_h >= 0);
-    if (K % kBK != 0 || ld_do % 8 != 0 || ldv % 8 != 0 || ldc % 8 != 0) return LP_ERR_UNSUPPORTED;
-    const int nb = batch->nb, nh = batch->nh;
-    LP_REQUIRE(nb > 0 && nh > 0 && batch->a_b >= 0 && batch->a_h >= 0 && batch->b_b >= 0 && batch->b_h >= 0 && batch->c_b >= 0 && batch->c_h >= 0);
-    const long long a_elems = (nb - 1) * batch->a_b + (nh - 1) * batch->a_h + (long long)(M - 1) * ld_do + K;
-    const long long b_elems = (nb - 1) * batch->b_b + (nh - 1) * batch->b_h + (long long)(N - 1) * ldv + K;
-    const long long c_elems = (nb - 1) * batch->c_b + (nh - 1) * batch->c_h + (long long)M * ldc;
-    const long long d_elems = (nb - 1) * d_b + (nh - 1) * d_h + (long long)(M - 1) * d_row_stride + 1;
-    if (a_elems >= (1LL << 31) || b_elems >= (1LL << 31) || c_elems >= (1LL << 32) || d_elems >= (1LL << 32)) return LP_ERR_UNSUPPORTED;
-    if ((batch->a_b | batch->a_h | batch->b_b | batch->b_h | batch->c_b | batch->c_h) % 8 != 0) return LP_ERR_UNSUPPORTED;
-    ConvGeom g{1, 1, M, K, 1, M, N, 1, 1, 1, 0};
-    ConvEpilogue ep{};
-    ep.out_bf16 = (unsigned short*)ds_bf16;
-    ep.ldo = ldc;
-    ep.n_store = ldc;  // the pad columns [N, ldc) are written as zeros, as lp_softmax_rows_bwd left them
-    ep.attn_p = (const unsigned short*)p_bf16;
-    ep.attn_d = d_rows;
-    ep.attn_scale = scale;
-    GemmExt gx{ld_do, ldv, nh, 0, (unsigned)(2 * batch->a_b), (unsigned)(2 * batch->a_h), (unsigned)(2 * batch->b_b), (unsigned)(2 * batch->b_h),
-               (unsigned)batch->c_b, (unsigned)batch->c_h, (unsigned)d_b, (unsigned)d_h, (unsigned)d_row_stride};
-    const Lattice lat{0, 1, 1, 0, 1, M, 0, 1, 1, 0, 1, 1};
-    hipStream_t st = (hipStream_t)stream;
-    if (ldc > 64) launch_igemm<128, kModeAttn>(d_out, v, g, lat, M, N, K, ep, st, &gx, nb * nh, (unsigned)(2 * a_elems), (unsigned)(2 * b_elems));
-    else launch_igemm<64, kModeAttn>(d_out, v, g, lat, M, N, K, ep, st, &gx, nb * nh, (unsigned)(2 * a_elems), (unsigned)(2 * b_elems));
-    return launch_status();
+    ConvProblem p;
+    if (const int rc = gemm_problem(p, kModeAttn, d_out, ld_do, v, ldv, ldc, 8, M, N, K, batch)) return rc;
+    const long long d_elems = (batch->nb - 1) * d_b + (batch->nh - 1) * d_h + (long long)(M - 1) * d_row_stride + 1;
+    if (d_elems >= (1LL << 32)) return LP_ERR_UNSUPPORTED;
+    p.ep.out_bf16 = (unsigned short*)ds_bf16;
+    p.ep.ldo = ldc;
+    p.ep.n_store = ldc;  // the pad columns [N, ldc) are written as zeros, as lp_softmax_rows_bwd left them
+    p.ep.attn_p = (const unsigned short*)p_bf16;
+    p.ep.attn_d = d_rows;
+    p.ep.attn_scale = scale;
+    p.igemm_cols = ldc;
+    p.gx.d_zb = (unsigned)d_b, p.gx.d_zh = (unsigned)d_h, p.gx.d_row = (unsigned)d_row_stride;
+    return run_conv(p, stream);
 }
 
 // dx[b][hi][wi][ci] = sum dy[b][ho][wo][co] * wd[ci][r][s][co] over taps with ho*st - pad + r == hi  (+ addend)
@@ -1669,8 +1732,10 @@ static int conv_dgrad_impl(const void* dy, const void* wd, const lp_conv_geom* g
         (long long)g.B * g.Hi * g.Wi * ldo >= (1LL << 32))
         return LP_ERR_UNSUPPORTED;
     const int N = g.Ci;
-    ConvEpilogue ep{(unsigned short*)dx_bf16, dx_f32, ldo, n_store > 0 ? n_store : N, bias, (const unsigned short*)addend,
-                    (const unsigned short*)relu_mask};
+    ConvProblem p = conv_problem(kModeDgrad, dy, wd, g, g.Hi, g.Wi, N, g.R * g.S * g.Co);
+    ConvEpilogue& ep = p.ep;
+    ep = ConvEpilogue{(unsigned short*)dx_bf16, dx_f32, ldo, n_store > 0 ? n_store : N, bias, (const unsigned short*)addend,
+                      (const unsigned short*)relu_mask};
     if (relu_bits != nullptr) {   // lp_conv_dgrad_bits: the ReLU mask at 1 bit per element of the dense bf16 result ([rows][N / 8] bytes)
         LP_REQUIRE(bn == nullptr && relu_mask == nullptr && dx_bf16 && !dx_f32 && ldo == N && ep.n_store == N);
         if (N % 8 != 0) return LP_ERR_UNSUPPORTED;
@@ -1691,43 +1756,29 @@ static int conv_dgrad_impl(const void* dy, const void* wd, const lp_conv_geom* g
         ep.mask_from_z = bn->mask_from_z;
         ep.relu_bits = (const unsigned char*)bn->relu_bits;
         ep.addend_half = bn->addend_half;
+        // (kEkAZB recomputes its output offsets from the row index: stride 1 is one launch on the full lattice)
         LP_REQUIRE(!ep.addend_half || (addend && bn->relu_bits && g.stride == 1));
     }
-    hipStream_t st = (hipStream_t)stream;
-    int n_launches = 0;
-    bool seg_ok = true;
-    auto launch = [&](const Lattice& lat) {
-        const int M = g.B * lat.nh * lat.nw, K = lat.nr * lat.ns * g.Co;
-        if (M <= 0) return;
-        const long long seg_rows = bn ? seg_split_rows(bn->seg_images, g.B, (long long)lat.nh * lat.nw, M) : M;
-        if (seg_rows < 0 || ++n_launches > 4) {
-            seg_ok = false;
-            return;
-        }
-        const int kind = pipe_dgrad_kind(ep);
-        const bool full_lattice = lat.hstep == 1 && lat.wstep == 1;   // (kEkAZB recomputes its output offsets from the row index)
-        if (ep.addend_half && !full_lattice) {   // (stride 1: required above)
-            seg_ok = false;
-            return;
-        }
-        if (kind >= 0 && (kind != kEkAZB || full_lattice) && pipe_eligible(ep, M, N, K, g.Co, seg_rows)) {
-            if (N > 64) launch_pipe_dgrad<128>(kind, dy, wd, g, lat, M, N, K, ep, st);
-            else launch_pipe_dgrad<64>(kind, dy, wd, g, lat, M, N, K, ep, st);
-        } else if (N > 64) launch_igemm<128, kModeDgrad>(dy, wd, g, lat, M, N, K, ep, st);
-        else launch_igemm<64, kModeDgrad>(dy, wd, g, lat, M, N, K, ep, st);
+    p.ek = pipe_dgrad_kind(ep);
+    // Every launch of this call, planned before any is enqueued: one on the full lattice (stride 1; conv_problem's) or one per parity class
+    // of (hi + pad, wi + pad) with the taps of the same parity only (stride 2: at most four).  The checks below see the whole list, so no
+    // error is returned after anything was enqueued.
+    struct DgradLaunch {
+        Lattice lat;
+        int M, K;
+        long long seg_rows;
+        ConvRoute route;
     };
-    if (bn && bn->seg_images > 0) {  // check every launch's segment boundary BEFORE anything is enqueued
-        if (bn->seg_images >= g.B) return LP_ERR_UNSUPPORTED;
-        const int hh[2] = {g.stride == 1 ? g.Hi : (g.Hi + 1) / 2, g.stride == 1 ? g.Hi : g.Hi / 2};
-        const int ww[2] = {g.stride == 1 ? g.Wi : (g.Wi + 1) / 2, g.stride == 1 ? g.Wi : g.Wi / 2};
-        for (int a = 0; a < 2; ++a)
-            for (int b = 0; b < 2; ++b)
-                if (hh[a] * ww[b] > 0 && ((long long)bn->seg_images * hh[a] * ww[b]) % kBM != 0) return LP_ERR_UNSUPPORTED;
-    }
+    DgradLaunch plan[4];
+    int n = 0;
+    auto add = [&](const Lattice& lat) {
+        const int M = g.B * lat.nh * lat.nw;
+        if (M <= 0) return;
+        plan[n++] = DgradLaunch{lat, M, lat.nr * lat.ns * g.Co, bn ? seg_split_rows(bn->seg_images, g.B, (long long)lat.nh * lat.nw, M) : M, {}};
+    };
     if (g.stride == 1) {
-        launch(Lattice{0, 1, g.Hi, 0, 1, g.Wi, 0, 1, g.R, 0, 1, g.S});
+        add(p.lat);
     } else {
-        // stride 2: one launch per parity class of (hi + pad, wi + pad); taps of the same parity only
         for (int ph = 0; ph < 2; ++ph)
             for (int pw = 0; pw < 2; ++pw) {
                 const int h0 = ((ph - g.pad) % 2 + 2) % 2, w0 = ((pw - g.pad) % 2 + 2) % 2;
@@ -1735,10 +1786,21 @@ static int conv_dgrad_impl(const void* dy, const void* wd, const lp_conv_geom* g
                 const int nr = ph < g.R ? (g.R - ph + 1) / 2 : 0, ns = pw < g.S ? (g.S - pw + 1) / 2 : 0;
                 // a class no tap reaches only copies addend (or zeros): the caller may declare dx already correct there
                 if (skip_empty_classes && nr * ns == 0) continue;
-                launch(Lattice{h0, 2, nh, w0, 2, nw, ph, 2, nr, pw, 2, ns});
+                add(Lattice{h0, 2, nh, w0, 2, nw, ph, 2, nr, pw, 2, ns});
             }
     }
-    if (!seg_ok) return LP_ERR_UNSUPPORTED;
+    auto problem_of = [&p](const DgradLaunch& e) {
+        p.lat = e.lat, p.M = e.M, p.K = e.K, p.seg_rows = e.seg_rows;
+    };
+    for (int i = 0; i < n; ++i) {
+        if (plan[i].seg_rows < 0) return LP_ERR_UNSUPPORTED;   // a BatchNorm segment boundary off this launch's 128-row tile grid
+        problem_of(plan[i]);
+        plan[i].route = route_conv(p, lp_switches());
+    }
+    for (int i = 0; i < n; ++i) {   // (lp_conv_last_kernel reports the last class's kernel)
+        problem_of(plan[i]);
+        launch_conv(plan[i].route, p, (hipStream_t)stream);
+    }
     return launch_status();
 }
 
@@ -1852,33 +1914,23 @@ extern "C" int lp_gemm_tn(const void* x, int ldx, const void* y, int ldy, void* 
     return launch_status();
 }
 
-// 7x7/2 stem on NHWC4 bf16 input (channel 3 = 0): weights [64][7+1][8][4] zero padded (K = 256)
+// 7x7/2 stem on NHWC4 bf16 input (channel 3 = 0): weights [64][7+1][8][4] zero padded (K = 256).  conv_stem2d_kernel (conv_res2d.h), or
+// with LP_STEM_2D=0 (A/B runs, bit-identity tests) and on the shapes it declines conv_igemm_kernel<64, stem>
 static int stem_fwd_impl(const void* x4, const void* w, const lp_conv_geom* geom, void* out_bf16, const lp_bn_fuse* bn,
                          lp_stream_t stream) {
     using namespace lp;
     LP_REQUIRE(x4 && w && geom_ok(geom) && out_bf16);
     ConvGeom g = to_geom(geom);
-    if (g.R != 7 || g.S != 7 || g.stride != 2 || g.pad != 3 || g.Ci != 4 || g.Co != 64) return LP_ERR_UNSUPPORTED;
-    const int M = g.B * g.Ho * g.Wo;
-    ConvEpilogue ep{(unsigned short*)out_bf16, nullptr, 64, 64};
+    if (!is_stem(g)) return LP_ERR_UNSUPPORTED;
+    ConvProblem p = conv_problem(kModeStem, x4, w, g, g.Ho, g.Wo, 64, 256);
+    p.gate = &LpSwitches::stem_2d;
+    p.ep = ConvEpilogue{(unsigned short*)out_bf16, nullptr, 64, 64};
     if (bn) {
         LP_REQUIRE(bn->sums && bn->seg_images >= 0);
-        if (seg_split_rows(bn->seg_images, g.B, (long long)g.Ho * g.Wo, M) < 0) return LP_ERR_UNSUPPORTED;
-        bn_fuse_begin(ep, bn);
+        if (seg_split_rows(bn->seg_images, g.B, (long long)g.Ho * g.Wo, p.M) < 0) return LP_ERR_UNSUPPORTED;
+        bn_fuse_begin(p.ep, bn);
     }
-    // conv_stem2d_kernel (conv_res2d.h): 16 x 16 output tiles, filter resident in LDS.  LP_STEM_2D=0 (A/B runs, bit-identity tests) keeps
-    // conv_igemm_kernel<64, stem>
-    if (conv_pipe_enabled() && lp_switches().stem_2d != 0 && g.Ho % 16 == 0 && g.Wo % 16 == 0 && g.Hi == 2 * g.Ho && g.Wi == 2 * g.Wo) {
-        const int ntiles = g.B * (g.Ho / 16) * (g.Wo / 16);
-        const int grid = ntiles < 2 * pipe_max_wgs() ? ntiles : 2 * pipe_max_wgs();
-        g_last_conv_kernel = LP_CONV_KERNEL_RES2D;
-        hipLaunchKernelGGL(conv_stem2d_kernel, dim3(grid), dim3(512), 0, (hipStream_t)stream, (const unsigned short*)x4, (const unsigned short*)w,
-                           (unsigned)(2ull * g.B * g.Hi * g.Wi * 4), g.B, g.Ho, g.Wo, ntiles, ep);
-    } else {
-        const Lattice lat{0, 1, g.Ho, 0, 1, g.Wo, 0, 1, g.R, 0, 1, g.S};
-        launch_igemm<64, kModeStem>(x4, w, g, lat, M, 64, 256, ep, (hipStream_t)stream);
-    }
-    return launch_status();
+    return run_conv(p, stream);
 }
 
 extern "C" int lp_stem_fwd(const void* x4, const void* w, const lp_conv_geom* geom, void* out_bf16, lp_stream_t stream) {

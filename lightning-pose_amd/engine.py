@@ -280,17 +280,8 @@ class Engine:
         out = fn()
         e1.record()
         if tag.startswith("conv_") and hasattr(self._lib, "lp_conv_last_kernel"):   # label the launch with the kernel that actually ran
-            k = self._lib.lp_conv_last_kernel()
-            if k == _lib.CONV_KERNEL_PIPE:
-                tag = tag.replace("conv_igemm_kernel", "conv_pipe_kernel")
-            elif k == _lib.CONV_KERNEL_PIPE_HALO:
-                tag = tag.replace("conv_igemm_kernel", "conv_pipe_kernel").replace(">", ",halo>")
-            elif k == _lib.CONV_KERNEL_RES2D:
-                tag = tag.replace("conv_igemm_kernel<64,", "conv_res2d_kernel<").replace("conv_igemm_kernel<64>", "conv_res2d_kernel<fwd>")
-            elif k == _lib.CONV_KERNEL_WGRAD_PIPE:
-                tag = tag.replace("conv_wgrad_kernel", "conv_wgrad_pipe_kernel")
-            elif k == _lib.CONV_KERNEL_WGRAD_NB:
-                tag = tag.replace("conv_wgrad_kernel", "conv_wgrad_nb_kernel")
+            for old, new in _lib.CONV_KERNEL_LABEL.get(self._lib.lp_conv_last_kernel(), ()):
+                tag = tag.replace(old, new)
         self.profile.append((tag, flops, e0, e1, nbytes, layer))
         return out
 

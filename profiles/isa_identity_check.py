@@ -32,9 +32,10 @@ def kernels(asm: str) -> dict[str, list[str]]:
     return out
 
 
-def compile_to_asm(src_text: str, common_text: str, workdir: str, tag: str) -> str:
-    with open(os.path.join(workdir, "lp_common.h"), "w") as fh:
-        fh.write(common_text.replace('"../../include/lp_hip.h"', f'"{os.path.join(ROOT, "include", "lp_hip.h")}"'))
+def compile_to_asm(src_text: str, headers: dict[str, str], workdir: str, tag: str) -> str:
+    for name, text in headers.items():   # every csrc/*.h of the same tree: lp_common.h and the kernel headers the source includes
+        with open(os.path.join(workdir, name), "w") as fh:
+            fh.write(text.replace('"../../include/lp_hip.h"', f'"{os.path.join(ROOT, "include", "lp_hip.h")}"'))
     src = os.path.join(workdir, f"{tag}.hip")
     with open(src, "w") as fh:
         fh.write(src_text)
@@ -49,6 +50,16 @@ def git_show(rev: str, path: str) -> str | None:
     return res.stdout if res.returncode == 0 else None
 
 
+def headers_at(rev: str) -> dict[str, str]:
+    names = subprocess.run(["git", "-C", ROOT, "ls-tree", "--name-only", f"{rev}:lightning-pose_amd/csrc"], capture_output=True, text=True,
+                           check=True).stdout.split()
+    return {n: git_show(rev, f"lightning-pose_amd/csrc/{n}") for n in names if n.endswith(".h")}
+
+
+def headers_here() -> dict[str, str]:
+    return {n: open(os.path.join(CSRC, n)).read() for n in os.listdir(CSRC) if n.endswith(".h")}
+
+
 def main() -> None:
     rev = sys.argv[1]
     files = sys.argv[2:] or sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
@@ -61,8 +72,8 @@ def main() -> None:
             print(f"{f}: not in {rev} (new file)")
             continue
         with tempfile.TemporaryDirectory() as a, tempfile.TemporaryDirectory() as b:
-            old = kernels(compile_to_asm(old_src, git_show(rev, "lightning-pose_amd/csrc/lp_common.h"), a, "k"))
-            new = kernels(compile_to_asm(new_src, open(os.path.join(CSRC, "lp_common.h")).read(), b, "k"))
+            old = kernels(compile_to_asm(old_src, headers_at(rev), a, "k"))
+            new = kernels(compile_to_asm(new_src, headers_here(), b, "k"))
         renamed = {k: k2 for k in old if k not in new for k2 in new if k2 not in old and new[k2] == old[k]}  # e.g. a function made a template
         for k in sorted(set(old) | set(new)):
             if k in renamed:
