@@ -14,7 +14,7 @@
  *     calls only enqueue - no device synchronisation, no host read-back
  *   - return value: 0 = LP_OK, < 0 = argument / shape error (nothing was launched), > 0 = hipError_t
  *   - re-entrant and thread-safe: no entry point keeps state between calls or reads the environment.  The only process-wide data is
- *     the table of A/B switches (LP_CONV_PIPE, LP_CONV_HALO, LP_CONV_RES2D, LP_INFER_PIPE, LP_GEMM_PIPE, LP_WGRAD_PIPE,
+ *     the table of A/B switches (LP_CONV_PIPE, LP_CONV_HALO, LP_PIPE_WRES, LP_CONV_RES2D, LP_INFER_PIPE, LP_GEMM_PIPE, LP_WGRAD_PIPE,
  *     LP_STEM_2D, LP_STEM_WGRAD_NB, LP_POOL_V2, LP_CONV_MAX_WGS, LP_BN_BWD_WGS_PER_CU), read from the environment ONCE when the library is loaded and immutable afterwards -
  *     except through lp_config_reload_env(), a test / A-B hook that must not run concurrently with other calls
  *   - limits: lp_bn_bwd_apply WITHOUT its terms_ws workspace covers C <= 2048 channels (the per-launch correction table then lives in
@@ -52,8 +52,8 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * e.g., the stream argument for an inserted flag without any error.  History: 131 = round 5 (decode `prune`, bn_bwd `terms_ws`), 140 = round 6,
  * 144 = the multi-view token assembly (lp_vit_mv_tokens_*), 145 = the camera geometry of the calibrated 3-D losses (lp_cam_*),
  * 146 = patch masking (lp_patch_mask_f32), 147 = LayerScale inside the LayerNorm walks (lp_layernorm_ls_*, the DINOv2 backbones),
- * 148 = the multi-view labeled batch with its 3-D augmentation (lp_mv3d_*). */
-#define LP_HIP_ABI_VERSION 148
+ * 148 = the multi-view labeled batch with its 3-D augmentation (lp_mv3d_*), 149 = lp_conv_last_resident. */
+#define LP_HIP_ABI_VERSION 149
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -212,6 +212,10 @@ typedef struct lp_conv_geom {
 #define LP_CONV_KERNEL_WGRAD_NB 9 /* conv_wgrad_nb_kernel: 3x3 / stride 1 weight gradient, input staged once for all nine taps (LP_WGRAD_NB=0 disables) */
 #define LP_CONV_KERNEL_RES2D 5     /* conv_res2d_kernel: 3x3 / stride 1, 64 -> 64 channels, 16 x 16 tiles, filter resident in LDS (LP_CONV_RES2D=0 disables) */
 int lp_conv_last_kernel(void);
+/* 1 if that launch was conv_pipe_kernel's weight-resident form (1x1 / stride 1 with K * column block * 2 <= 64 KB: the weight panel stays
+ * in LDS for the workgroup's whole walk; LP_PIPE_WRES=0 disables it, =2 takes it wherever the shape allows), else 0.  The kernel id above
+ * stays LP_CONV_KERNEL_PIPE for it.  Diagnostic only. */
+int lp_conv_last_resident(void);
 
 /* w: bf16 [Co][R][S][Ci] (Ci % 64 == 0).  Output row-major [B*Ho*Wo][ldo], columns < n_store written. */
 int lp_conv_fwd(const void* x, const void* w, const lp_conv_geom* geom, const float* bias, void* out_bf16, float* out_f32, int ldo,

@@ -16,6 +16,7 @@ static LpSwitches read_switches() {
     LpSwitches s;
     s.conv_pipe = env_int("LP_CONV_PIPE", 1);       // 0: every convolution on conv_igemm_kernel / conv_wgrad_kernel
     s.conv_halo = env_int("LP_CONV_HALO", 1);       // 0: the 3x3 layers on the per-tap ring
+    s.pipe_wres = env_int("LP_PIPE_WRES", 1);       // 0: no weight-resident form of conv_pipe_kernel; 2: wherever its shape rule admits it (A/B runs)
     s.conv_res2d = env_int("LP_CONV_RES2D", 1);     // 0: layer1's 64 -> 64 3x3 layers on the HALO form
     s.infer_pipe = env_int("LP_INFER_PIPE", 1);     // 0: lp_conv_fwd_act on conv_igemm_kernel<infer>
     s.gemm_pipe = env_int("LP_GEMM_PIPE", 1);       // 0: the Linear layers on conv_igemm_kernel

@@ -1084,6 +1084,7 @@ static void bn_fuse_begin(ConvEpilogue& ep, const lp_bn_fuse* bn) {
 // per-launch timings with the kernel that actually ran; tests assert the path they mean to exercise).  Assigned by launch_conv() and by
 // the weight-gradient entry points, nowhere else.
 static thread_local int g_last_conv_kernel = LP_CONV_KERNEL_IGEMM;
+static thread_local int g_last_conv_resident = 0;   // ... and whether it was conv_pipe_kernel's weight-resident form (lp_conv_last_resident)
 
 // ---- forward / data-gradient dispatch.  Every forward, inference, Linear / GEMM, data-gradient and stem entry point describes its launch
 // as a ConvProblem; the admits_*() functions say which kernel families the geometry and the store pass admit (shape rules: they read no
@@ -1094,6 +1095,7 @@ struct ConvRoute {
     int bn;       // column block: 64 or 128
     int mode;     // kMode*: the problem's
     int ek;       // conv_pipe_kernel's store-pass form (kEk*)
+    bool wres;    // LP_CONV_KERNEL_PIPE only: the weight-resident form (the reported kernel id stays conv_pipe's)
 };
 constexpr int kNoKernel = -1;
 
@@ -1193,6 +1195,21 @@ static bool admits_halo(const ConvProblem& p) {
     return (p.ek == kEkNone || p.ek == kEkInfer || p.ek == kEkZ) && halo_shape_ok(p.g, p.M, conv_ck(p), p.N > 64 ? 384 : 512);
 }
 
+// ... its weight-resident form (conv_pipe.h: WRES): the training store passes of a 1x1 / stride 1 / pad 0 problem on the full lattice whose
+// BN x K weight panel fits the 64 KB beside the pixel ring (K <= 256 at 128 columns, K <= 512 at 64).  Asked once admits_pipe() has passed.
+static bool admits_wres(const ConvProblem& p) {
+    if (!(p.ek == kEkNone || p.ek == kEkZ || p.ek == kEkAZB || p.ek == kEkPlain || p.ek == kEkPB)) return false;
+    if (p.g.R != 1 || p.g.S != 1 || p.g.stride != 1 || p.g.pad != 0 || p.lat.hstep != 1 || p.lat.wstep != 1 || p.K != conv_ck(p)) return false;
+    return (long long)p.K * (p.N > 64 ? 128 : 64) * 2 <= 64 * 1024;
+}
+
+// The performance rule of the weight-resident form (LP_PIPE_WRES=2 does not ask): the launch classes that measured faster than the ring
+// by more than the ring's own run-to-run spread (profiles/pipe_wres_layer_table.txt).  Every eligible data gradient
+// did, and every forward launch that does not reduce its channel count (N >= K: conv3 and layer1's projection shortcut).  The reducing
+// forward launches (conv1 of the blocks whose input has 256 channels: K = 256, N = 64 / 128) read four or two times what they write and
+// already run at the HBM rate (5.2 TB/s of algorithmic bytes): their K step is not what they wait for, and they measured equal.
+static bool wres_tuned(const ConvProblem& p) { return p.mode == kModeDgrad || p.N >= p.K; }
+
 // conv_res2d_kernel: whatever conv_pipe_kernel would take of layer1's 3x3 layers, with the store passes kEkNone and kEkZ and no bias.  Its
 // inference store pass (lp_conv_fwd_act) is the exception twice over: it adds the bias but no residual, and it asks for the shape alone
 // (whatever has that shape there passes pipe_shape_ok as well).
@@ -1207,14 +1224,18 @@ static bool admits_res2d(const ConvProblem& p) {
 // LP_CONV_PIPE=0 sends everything to conv_igemm_kernel (A/B runs, and the tests that compare the kernels bit for bit), and so does the
 // entry point's own switch (ConvProblem::gate) when it is 0; LP_CONV_RES2D=0 leaves layer1's 3x3 layers to conv_pipe_kernel's HALO form,
 // LP_CONV_HALO=0 keeps the 3x3 layers on its per-tap ring.  A shape rule is asked only once the switches let its family run, so
-// halo_shape_ok's memo sees the geometries that can take the HALO form and no others.
+// halo_shape_ok's memo sees the geometries that can take the HALO form and no others.  LP_PIPE_WRES: 1 = the weight-resident form of
+// conv_pipe_kernel where its shape rule and its performance rule pass, 0 = the ring everywhere, 2 = wherever the shape rule passes (A/B runs).
 static ConvRoute route_conv(const ConvProblem& p, const LpSwitches& sw) {
     const bool pipe = sw.conv_pipe != 0 && (p.gate == nullptr || sw.*p.gate != 0);
-    if (p.mode == kModeStem) return ConvRoute{pipe && stem2d_shape_ok(p.g) ? LP_CONV_KERNEL_RES2D : LP_CONV_KERNEL_IGEMM, 64, p.mode, p.ek};
-    if (pipe && sw.conv_res2d != 0 && admits_res2d(p)) return ConvRoute{LP_CONV_KERNEL_RES2D, 64, p.mode, p.ek};
-    if (pipe && admits_pipe(p))
-        return ConvRoute{sw.conv_halo != 0 && admits_halo(p) ? LP_CONV_KERNEL_PIPE_HALO : LP_CONV_KERNEL_PIPE, p.N > 64 ? 128 : 64, p.mode, p.ek};
-    return ConvRoute{p.igemm_form ? LP_CONV_KERNEL_IGEMM : kNoKernel, p.igemm_cols > 64 ? 128 : 64, p.mode, p.ek};
+    if (p.mode == kModeStem) return ConvRoute{pipe && stem2d_shape_ok(p.g) ? LP_CONV_KERNEL_RES2D : LP_CONV_KERNEL_IGEMM, 64, p.mode, p.ek, false};
+    if (pipe && sw.conv_res2d != 0 && admits_res2d(p)) return ConvRoute{LP_CONV_KERNEL_RES2D, 64, p.mode, p.ek, false};
+    if (pipe && admits_pipe(p)) {
+        if (sw.conv_halo != 0 && admits_halo(p)) return ConvRoute{LP_CONV_KERNEL_PIPE_HALO, p.N > 64 ? 128 : 64, p.mode, p.ek, false};
+        const bool wres = sw.pipe_wres != 0 && admits_wres(p) && (sw.pipe_wres == 2 || wres_tuned(p));
+        return ConvRoute{LP_CONV_KERNEL_PIPE, p.N > 64 ? 128 : 64, p.mode, p.ek, wres};
+    }
+    return ConvRoute{p.igemm_form ? LP_CONV_KERNEL_IGEMM : kNoKernel, p.igemm_cols > 64 ? 128 : 64, p.mode, p.ek, false};
 }
 
 // ---- launch ----
@@ -1270,7 +1291,7 @@ static void launch_stem2d(const ConvProblem& p, hipStream_t st) {
                        (unsigned)(2ull * g.B * g.Hi * g.Wi * 4), g.B, g.Ho, g.Wo, ntiles, p.ep);
 }
 
-template <int BN, int MODE, int EK, bool HALO = false>
+template <int BN, int MODE, int EK, bool HALO = false, bool WRES = false>
 static void launch_pipe(const ConvProblem& p, hipStream_t st) {
     const ConvGeom& g = p.g;
     const int tm = (p.M + kPM - 1) / kPM, tn = p.N / BN, ntiles = tm * tn;
@@ -1279,7 +1300,7 @@ static void launch_pipe(const ConvProblem& p, hipStream_t st) {
     const unsigned x_bytes = (unsigned)(2ull * (MODE == kModeDgrad ? (size_t)g.B * g.Ho * g.Wo * g.Co : (size_t)g.B * g.Hi * g.Wi * g.Ci));
     const unsigned w_bytes = (unsigned)(2ull * (size_t)p.N * g.R * g.S * ck);
     const HaloDivs hd{make_fastdiv(g.Hi), make_fastdiv(g.Wi + 2), make_fastdiv(g.Hi + 2)};
-    hipLaunchKernelGGL((conv_pipe_kernel<BN, MODE, EK, HALO>), dim3(grid), dim3(512), 0, st, (const unsigned short*)p.x, (const unsigned short*)p.w,
+    hipLaunchKernelGGL((conv_pipe_kernel<BN, MODE, EK, HALO, WRES>), dim3(grid), dim3(512), 0, st, (const unsigned short*)p.x, (const unsigned short*)p.w,
                        x_bytes, w_bytes, g, p.lat, make_fastdiv(p.lat.nh * p.lat.nw), make_fastdiv(p.lat.nw), p.M, p.N, p.K, tn, ntiles, p.ep, hd);
 }
 
@@ -1292,6 +1313,15 @@ static void launch_conv_bn(const ConvRoute& r, const ConvProblem& p, hipStream_t
             case kModeDgrad: return launch_igemm<BN, kModeDgrad>(p, st);
             case kModeInfer: return launch_igemm<BN, kModeInfer>(p, st);
             default: return launch_igemm<BN, kModeAttn>(p, st);
+        }
+    }
+    if (r.wres) {   // (route_conv: the training store passes of a 1x1 problem; never with halo)
+        switch (r.ek) {
+            case kEkNone: return launch_pipe<BN, kModeFwd, kEkNone, false, true>(p, st);
+            case kEkZ: return launch_pipe<BN, kModeDgrad, kEkZ, false, true>(p, st);
+            case kEkAZB: return launch_pipe<BN, kModeDgrad, kEkAZB, false, true>(p, st);
+            case kEkPB: return launch_pipe<BN, kModeDgrad, kEkPB, false, true>(p, st);
+            default: return launch_pipe<BN, kModeDgrad, kEkPlain, false, true>(p, st);
         }
     }
     const bool halo = r.kernel == LP_CONV_KERNEL_PIPE_HALO;   // (route_conv: kEkNone, kEkInfer and kEkZ only)
@@ -1310,6 +1340,7 @@ static void launch_conv_bn(const ConvRoute& r, const ConvProblem& p, hipStream_t
 // form of kEkAZB, ...) has no instantiation.
 static void launch_conv(const ConvRoute& r, const ConvProblem& p, hipStream_t st) {
     g_last_conv_kernel = r.kernel;
+    g_last_conv_resident = r.wres ? 1 : 0;
     if (r.kernel == LP_CONV_KERNEL_RES2D) {
         switch (r.mode) {
             case kModeStem: return launch_stem2d(p, st);
@@ -1624,6 +1655,7 @@ static int conv_fwd_impl(const void* x, const void* w, const lp_conv_geom* geom,
 }
 
 extern "C" int lp_conv_last_kernel(void) { return lp::g_last_conv_kernel; }
+extern "C" int lp_conv_last_resident(void) { return lp::g_last_conv_resident; }
 
 extern "C" int lp_conv_fwd(const void* x, const void* w, const lp_conv_geom* geom, const float* bias, void* out_bf16, float* out_f32,
                            int ldo, int n_store, lp_stream_t stream) {
@@ -1851,6 +1883,7 @@ static int conv_wgrad_impl(const void* x, const void* dy, const lp_conv_geom* ge
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     g_last_conv_kernel = p.kernel;
+    g_last_conv_resident = 0;
     if (p.kernel == LP_CONV_KERNEL_WGRAD_NB) {
         if (p.bn == 128) launch_wgrad_nb<128>(p, x, dy, g, dw, ws, st);
         else launch_wgrad_nb<64>(p, x, dy, g, dw, ws, st);
@@ -1959,6 +1992,7 @@ extern "C" int lp_stem_wgrad(const void* x4, const void* dy, const lp_conv_geom*
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     g_last_conv_kernel = p.kernel;
+    g_last_conv_resident = 0;
     if (p.kernel == LP_CONV_KERNEL_STEM_WGRAD_NB)   // one workgroup per pixel slice forms all 256 gradient rows from the staged input neighbourhood
         hipLaunchKernelGGL(stem_wgrad_nb_kernel, dim3(p.split), dim3(256), 0, st, xs, dys, (unsigned)(8ull * g.B * g.Hi * g.Wi),
                            (unsigned)(128ull * M), g, M, p.per, dhw, dwo, ws);

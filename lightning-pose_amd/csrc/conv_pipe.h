@@ -101,7 +101,15 @@ struct HaloDivs {
     FastDiv h, wp, hp;   // image height, padded width W + 2, padded height H + 2
 };
 
-template <int BN, int MODE, int EK, bool HALO = false>
+//
+// WRES (1x1, stride 1, pad 0 with K * BN * 2 <= 64 KB - conv3 forward and the conv1 data gradients of the trunk): the weights do not ride the
+// ring.  A workgroup keeps its column block n0 for its whole walk wherever the grid's stride is a multiple of tiles_n (every trunk shape),
+// so the ring above re-fetches the same BN x K weight panel once per tile: a third of the bytes and of the direct-to-LDS instructions of
+// every K step.  Here the panel is RESIDENT: K / 64 slices beside the ring, each the exact image of a weight stage ([BN rows][64 k], same
+// source-side swizzle; fragment addresses = the ring form's + kt * kStageB), loaded once before the walk and again only where the walk meets
+// another column block; the ring's three stages hold pixels alone (32 KB each, 4 loads per thread and K step).  96 + 64 = 160 KB of LDS.
+// The K order and every rounding point are the ring form's: outputs and BatchNorm partial sums are bit-identical to it.
+template <int BN, int MODE, int EK, bool HALO = false, bool WRES = false>
 __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __restrict__ X, const unsigned short* __restrict__ Wt,
                                                         unsigned x_bytes, unsigned w_bytes, ConvGeom g, Lattice lat, FastDiv div_img,
                                                         FastDiv div_row, int M, int N, int K, int tiles_n, int ntiles, ConvEpilogue ep,
@@ -109,9 +117,11 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
     static_assert((MODE == kModeFwd && (EK == kEkNone || EK == kEkInfer || EK == kEkGeluBwd || EK == kEkGeluFwd)) ||
                       (MODE == kModeDgrad && EK != kEkNone && EK != kEkInfer && EK != kEkGeluBwd && EK != kEkGeluFwd),
                   "trunk convolutions only");
+    static_assert(!(HALO && WRES), "the weight-resident form is the per-tap ring's");
+    static_assert(!WRES || EK == kEkNone || EK == kEkZ || EK == kEkAZB || EK == kEkPlain || EK == kEkPB, "weight-resident form: the training store passes");
     constexpr int NT = BN / 64;                  // 32-channel MFMA blocks per wave along N (wave tile 64 pixels x NT*32 channels)
     constexpr int NBL = BN / 64;                 // weight rows each thread stages per K step
-    constexpr int kStageA = HALO ? 0 : kPM * kPRowB, kStageB = BN * kPRowB, kStage = kStageA + kStageB;
+    constexpr int kStageA = HALO ? 0 : kPM * kPRowB, kStageB = BN * kPRowB, kStage = kStageA + (WRES ? 0 : kStageB);
     constexpr int kHaloRows = BN == 64 ? 512 : 384;   // rows of a halo image (host-checked against the geometry: pipe_halo_rows)
     constexpr int kHaloB = kHaloRows * kPRowB, NA = kHaloRows / 64;   // bytes; direct-to-LDS loads per thread and halo image
     // Ring depth.  Per-tap ring: 3 stages of 48 KB (two K steps of loads in flight) is what LDS holds.  HALO form: a stage is only the weights
@@ -119,8 +129,10 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
     // round 5 (-DLP_HALO_STAGES=4, profiles/r05h_halo_stages.txt) - no difference in any 3x3 layer, so their K step is not waiting for its weights.
     constexpr int NST = HALO ? LP_HALO_STAGES : 3;
     static_assert(NST == 3 || NST == 4, "ring depth");
-    __shared__ __attribute__((aligned(16))) unsigned char smem[NST * kStage + (HALO ? 2 * kHaloB : 0)];
+    constexpr int kPanelB = WRES ? 64 * 1024 : 0;   // the resident weight panel: K / 64 slices of kStageB bytes (host-checked: K * BN * 2 <= 64 KB)
+    __shared__ __attribute__((aligned(16))) unsigned char smem[NST * kStage + (HALO ? 2 * kHaloB : 0) + kPanelB];
     unsigned char* const halo0 = smem + NST * kStage;
+    unsigned char* const panel0 = smem + NST * kStage;   // (WRES)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -150,7 +162,7 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
     auto setup = [&](int vt) {
         if (vt >= ntiles) {   // past the end of the walk: the ring keeps turning on loads that fetch nothing (zeros), so the counted waits stay valid
 #pragma unroll
-            for (int i = 0; i < 4; ++i) vmask[i] = 0u, rowoff[i] = 0u;
+            for (int i = 0; i < 4; ++i) vmask[i] = 0u, rowoff[i] = 0u, voff[i] = ~0u;   // (voff: WRES - the other forms derive it per tap)
 #pragma unroll
             for (int i = 0; i < NBL; ++i) wrow[i] = ~0u;
             tir = tis = tc = 0;
@@ -177,6 +189,10 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
             }
             const int oy = halved ? (py[i] >> 1) : py[i], ox = halved ? (px[i] >> 1) : px[i];
             rowoff[i] = (unsigned)(((b * src_h + oy) * src_w + ox) * ck + lchunk * 8) * 2u;
+            if (WRES) {   // one tap that every pixel of the lattice has (1x1, pad 0: host-checked) - the step's offsets are final here, no per-tap state kept
+                voff[i] = pv ? rowoff[i] : ~0u;
+                continue;
+            }
             unsigned mask = 0;
             if (pv) {
                 for (int ir = 0; ir < lat.nr; ++ir)
@@ -197,7 +213,7 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
             vmask[i] = mask;
         }
 #pragma unroll
-        for (int i = 0; i < NBL; ++i) wrow[i] = (unsigned)((n0 + lrow + 64 * i) * ldw + lchunk * 8) * 2u;   // (N % BN == 0: host-checked)
+        for (int i = 0; i < (WRES ? 0 : NBL); ++i) wrow[i] = (unsigned)((n0 + lrow + 64 * i) * ldw + lchunk * 8) * 2u;   // (N % BN == 0: host-checked)
         tir = tis = tc = 0;
     };
 
@@ -217,7 +233,7 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
             if (++tir == 9) tir = 0, tc += kBK;
             return;
         }
-        if (tc == 0) {   // entering a filter tap: its per-row offsets (an invalid tap gets ~0 -> the range check returns zeros)
+        if (!WRES && tc == 0) {   // entering a filter tap: its per-row offsets (an invalid tap gets ~0 -> the range check returns zeros)
             const int tr = lat.r0 + lat.rstep * tir, ts = lat.s0 + lat.sstep * tis;
             const int qr = halved ? (tr >> 1) : tr, qs = halved ? (ts >> 1) : ts;
             const unsigned tapoff_b = (unsigned)(((MODE == kModeDgrad) ? -(qr * src_w + qs) : (qr * src_w + qs)) * ck) * 2u;
@@ -230,9 +246,11 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
             }
         }
         is_soff_a = (unsigned)tc * 2u;
-        is_soff_b = wtap + is_soff_a;
+        if (!WRES) {   // (WRES: the weights are resident, a step fetches pixels only)
+            is_soff_b = wtap + is_soff_a;
 #pragma unroll
-        for (int i = 0; i < NBL; ++i) is_w[i] = wrow[i];
+            for (int i = 0; i < NBL; ++i) is_w[i] = wrow[i];
+        }
         is_dst = smem + st * kStage + wave * (8 * kPRowB);
         tc += kBK;
         if (tc >= ck) {
@@ -258,8 +276,17 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
     auto load_step = [&](int st) {
         prep_step(st);
 #pragma unroll
-        for (int i = 0; i < (HALO ? NBL : 4 + NBL); ++i) issue_load(i);
+        for (int i = 0; i < (HALO ? NBL : WRES ? 4 : 4 + NBL); ++i) issue_load(i);
         advance_tile();
+    };
+    // WRES: the whole BN x K weight panel of column block n0 -> its K / 64 resident slices; per slice the loads of a ring step's weight side
+    // (NBL per thread, same rows, same swizzle on the source address).  1x1: a weight row is K elements.
+    auto panel_load = [&](const int n0) {
+        for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+            for (int i = 0; i < NBL; ++i)
+                buf_load16_lds(rsrc_w, panel0 + kt * kStageB + (i * 64 + wave * 8) * kPRowB, (unsigned)((n0 + lrow + 64 * i) * ldw + lchunk * 8) * 2u,
+                               (unsigned)(kt * (kBK * 2)));
     };
 
     // ---- HALO loader: one halo image (a tile's padded-raster neighbourhood x one 64-channel slice) ahead of the MFMAs
@@ -321,7 +348,7 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) koff[kk] = (unsigned)(((kk * 2 + fg) ^ fsw) * 16);
     const unsigned a_row = (unsigned)((wm * 64 + fr) * kPRowB);                   // pixel rows of this wave
-    const unsigned b_row = (unsigned)(kStageA + (wn * (NT * 32) + fr) * kPRowB);  // weight rows of this wave
+    const unsigned b_row = (unsigned)((WRES ? 0 : kStageA) + (wn * (NT * 32) + fr) * kPRowB);  // weight rows of this wave (WRES: inside a panel slice)
 
     f32x16 acc[2][NT];
     // `spread`: issue the prepared step's loads between the k-slices (2 after the first slice's MFMAs have been queued, then 2, 1, 1)
@@ -337,8 +364,9 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
     // HALO: rows of the tile's pixels inside the halo image (per tile), the halo image the MFMAs read, its tap, and whether the
     // loader still has pieces of the next halo image to issue during this K step
     int ploc[2] = {0, 0}, uloc[2] = {0, 0}, mh_buf = 0, mh_tap = 0;
-    auto mma_stage = [&](int st, const bool spread) {
+    auto mma_stage = [&](int st, const bool spread, const int mkt) {   // mkt: the K step inside the tile (WRES: its slice of the resident panel)
         const unsigned char* sb = smem + st * kStage;
+        const unsigned char* sbw = WRES ? panel0 + mkt * kStageB : sb;
         bf16x8 a[NS][2], b[NS][NT];
         const unsigned char* ha[2] = {smem, smem};
         unsigned hk[2][4] = {};
@@ -362,7 +390,7 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
-                b[set][nt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u16x8*>(sb + b_row + nt * (32 * kPRowB) + koff[kk]));
+                b[set][nt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u16x8*>(sbw + b_row + nt * (32 * kPRowB) + koff[kk]));
         };
 #pragma unroll
         for (int kk = 0; kk < NS - 1; ++kk) fetch(kk, kk);
@@ -393,6 +421,8 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
                 } else if (kk == 2) {
                     if (NBL == 2) issue_load(1);
                 }
+            } else if (spread && WRES) {   // the step's four pixel loads, one behind each k-slice
+                issue_load(kk);
             } else if (spread) {
                 constexpr int NL = 4 + NBL;
                 if (kk == 0) {
@@ -477,6 +507,7 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
         // kernel's busy cycles, 54 % on the K <= 128 launches where the store pass is most of the tile, profiles/r05_pmc_mfma_spec1.json.)
         constexpr bool kPad = LP_FWD_CORNER_PAD != 0;   // (A/B builds: 1 = rounds 3 - 4's padded rows)
         constexpr int ROWB = NT * 64 + (kPad ? 16 : 0);
+        static_assert(!(WRES && kPad), "the padded corner does not fit a pixel-only stage");
         unsigned char* stg = stg_all + wave * (32 * ROWB);
         const int wkey = kPad ? 0 : NT == 2 ? (fr & 15) : ((fr >> 1) & 7);
         u16x8 radd[2][32 / RP] = {};   // inference: this lane's pieces of the residual, all 8 requested before the conversion / staging work
@@ -621,8 +652,17 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
         // fp32 row of the wave's channels + pad.  (The XOR-swizzled unpadded layout of the forward's corner was tried here too, round 5: the
         // padded rows' read-back groups have 2-way conflicts - SQ_LDS_BANK_CONFLICT 9 - 16 % of these kernels' busy cycles - but the data gradients
         // sit at the register cap, and the swizzle's address arithmetic made three of them spill: tests/test_kernel_resources.py.)
-        constexpr int ROWF = NT * 128 + 16;
+        // WRES, BN = 128: the free stage is a pixel stage of 32 KB = 8 waves x 16 rows x 256 B, no room for the pad.  The rows are unpadded
+        // there and the 16-B slot c of row r sits at position c ^ r: the 16 pixels of a write group (one slot, rows 0 .. 15) hit 16 different
+        // positions, and so do the 2 rows x 8 even slots of a read group.  The lane's part of the key is folded into ONE base offset per
+        // direction and the compile-time part is a single XOR on it (the slot constants are even, the rows 256 B), which this form's
+        // registers can afford: it has no weight-side loader state.
+        constexpr bool kSwz = WRES && NT == 2;
+        constexpr int ROWF = kSwz ? 256 : NT * 128 + 16;
+        static_assert(!WRES || 8 * 16 * ROWF <= kStage, "the data gradient's corners fit the stage consumed last");
         unsigned char* stg = stg_all + wave * (16 * ROWF);
+        const unsigned wxor = (unsigned)((fr & 15) * 256 + ((fg ^ (fr & 15)) << 4));      // (kSwz) writes: row fr & 15, slot (even constant + fg) ^ row
+        const unsigned rxor = (unsigned)(prow * 256 + (((2 * pc) ^ prow) << 4));          // (kSwz) reads: row ps * 8 + prow, slots 2 pc and 2 pc + 1
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if ((fr >> 4) == h) {   // the 16 pixels of this half write their 4-channel runs
@@ -631,15 +671,22 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const f32x4 p4 = {acc[mt][nt][4 * j], acc[mt][nt][4 * j + 1], acc[mt][nt][4 * j + 2], acc[mt][nt][4 * j + 3]};
-                        *reinterpret_cast<f32x4*>(stg + (fr & 15) * ROWF + (nt * 32 + 8 * j + 4 * fg) * 4) = p4;
+                        if (kSwz) *reinterpret_cast<f32x4*>(stg + (wxor ^ (unsigned)((nt * 8 + 2 * j) << 4))) = p4;
+                        else *reinterpret_cast<f32x4*>(stg + (fr & 15) * ROWF + (nt * 32 + 8 * j + 4 * fg) * 4) = p4;
                     }
             }
             __builtin_amdgcn_wave_barrier();
             f32x4 lo_[PH], hi_[PH];
 #pragma unroll
             for (int ps = 0; ps < PH; ++ps) {
-                lo_[ps] = *reinterpret_cast<const f32x4*>(stg + (ps * RP + prow) * ROWF + pc * 32);
-                hi_[ps] = *reinterpret_cast<const f32x4*>(stg + (ps * RP + prow) * ROWF + pc * 32 + 16);
+                if (kSwz) {
+                    const unsigned o = (unsigned)(ps * RP * ROWF) + (rxor ^ (unsigned)(((ps * RP) & 15) << 4));   // (RP = 8: the row's key is prow ^ 8 ps)
+                    lo_[ps] = *reinterpret_cast<const f32x4*>(stg + o);
+                    hi_[ps] = *reinterpret_cast<const f32x4*>(stg + (o ^ 16u));
+                } else {
+                    lo_[ps] = *reinterpret_cast<const f32x4*>(stg + (ps * RP + prow) * ROWF + pc * 32);
+                    hi_[ps] = *reinterpret_cast<const f32x4*>(stg + (ps * RP + prow) * ROWF + pc * 32 + 16);
+                }
             }
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -701,6 +748,14 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
         halo_advance();
     }
     setup(ld_vt);
+    // WRES: the column block whose panel is resident.  The first tile's panel is issued BEFORE the ring's first two steps, so the first
+    // counted wait of the walk (which leaves only the younger of those steps in flight) covers it.
+    int pn0 = -1;
+    if (WRES && (int)blockIdx.x < ntiles) {
+        const int tile = xcd_remap(blockIdx.x, ntiles);
+        pn0 = (tile - (tile / tiles_n) * tiles_n) * BN;
+        panel_load(pn0);
+    }
 #pragma unroll
     for (int st = 0; st < NST - 1; ++st) load_step(st);
     int cur = 0;   // stage of the K step the MFMAs are about to consume
@@ -720,6 +775,14 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
                 ploc[mt] = padded(mc) - pbase;
                 uloc[mt] = ploc[mt] - 2 * (padded_row(mc) - rr0);
             }
+        }
+        if (WRES && n0 != pn0) {   // (workgroup-uniform) another column block in the middle of the walk (a segment change does not touch the weights)
+            // every wave passed the barrier behind the previous tile's K loop, i.e. is past its last fragment read of the old panel; the new
+            // panel's loads are younger than the ring's two steps in flight, so they are not in any counted wait: wait for everything once
+            // (this wave's share; the first K step's barrier publishes all of it)
+            panel_load(n0);
+            pn0 = n0;
+            LP_WAIT_VM(0);
         }
         if (n0 != st_n0 || seg_off != st_seg_off) {   // (workgroup-uniform) new column block / BatchNorm segment
             // the stage the previous tile consumed last is free until this tile's first K step has passed its barrier
@@ -755,6 +818,7 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
             else if (HALO && NST == 4) LP_WAIT_VM(2);
             else if (HALO && NBL == 2) LP_WAIT_VM(2);
             else if (HALO) LP_WAIT_VM(1);
+            else if (WRES) LP_WAIT_VM(4);     // (the next step's four pixel loads)
             else if (NBL == 2) LP_WAIT_VM(6);
             else LP_WAIT_VM(5);
             LP_RAW_BARRIER();              // ... everyone's have, and everyone is done reading the stage refilled next
@@ -762,11 +826,11 @@ __global__ __launch_bounds__(512) void conv_pipe_kernel(const unsigned short* __
             const int nxt = cur == 0 ? NST - 1 : cur - 1;   // (cur + NST - 1) % NST: the stage consumed at the previous step
             if (kSpread || HALO) {
                 prep_step(nxt);
-                mma_stage(cur, true);
+                mma_stage(cur, true, kt);
                 advance_tile();
             } else {
                 load_step(nxt);
-                mma_stage(cur, false);
+                mma_stage(cur, false, kt);
             }
             cur = cur == NST - 1 ? 0 : cur + 1;
             if (HALO && ++mh_tap == 9) {   // the slice is consumed: the MFMAs move to the other halo image, the loader to the one after it
