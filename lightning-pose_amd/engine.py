@@ -116,6 +116,58 @@ def build_head(feat_channels: int, stride: int, num_keypoints: int, downsample_f
     return head
 
 
+def place_head(head: list[ConvP], off: int, wd: int) -> tuple[int, int]:
+    """Give the head's layers their places in the flat buffers - weight, then bias, from ``off``; the transposed copy from ``wd`` - and
+    return the offsets behind them.  Every plan ends with this call, so the head is the tail of the buffers."""
+    for c in head:
+        c.w_off, c.wd_off = off, wd
+        off += c.numel
+        wd += c.numel
+        c.bias_off = off
+        off += c.Ci
+    return off, wd
+
+
+class HeadPlan:
+    """The plan of a head on its own (HeadEngine): what EngineCore asks of a plan and nothing else."""
+
+    def __init__(self, head: list[ConvP]):
+        self.head = head
+        self.convs = list(head)
+        self.n_backbone = self.n_running = 0
+        self.n_total, self.n_wd = place_head(head, 0, 0)
+
+    def group_ranges(self) -> dict[str, tuple[int, int]]:
+        return {"backbone": (0, 0), "head": (0, self.n_total)}
+
+
+_PARTS_LIMIT = {None: "batches", 1: "one batch", 2: "at most two batches"}
+
+
+def image_parts(images, multiple: int, max_parts: int | None, of: str = "") -> tuple[list[torch.Tensor], int, int, int]:
+    """The checks every forward pass makes before it hands raw pointers to the kernels, and the split of a joint pass:
+    ``images`` (B,3,H,W), or a list of such batches -> (contiguous fp32 batches, images in all, H, W).  H and W must be multiples of
+    ``multiple`` (``of`` names it in the message), the batches at most ``max_parts`` (None: any number) and equally sized."""
+    parts = list(images) if isinstance(images, (list, tuple)) else [images]
+    for p_ in parts:
+        ops.require_device(p_)
+    parts = [p_.to(torch.float32).contiguous() for p_ in parts]
+    if parts[0].dim() != 4 or parts[0].shape[1] != 3:
+        raise ValueError(f"images must be (B, 3, H, W), got {tuple(parts[0].shape)}")   # (raw pointers from here on)
+    _, _, H, W = parts[0].shape
+    if H % multiple or W % multiple:
+        raise ValueError(f"image size must be a multiple of {of}{multiple}, got {H}x{W}")
+    if (max_parts is not None and len(parts) > max_parts) or any(p_.shape[1:] != parts[0].shape[1:] for p_ in parts):
+        raise ValueError(f"a joint pass takes {_PARTS_LIMIT[max_parts]} of equally sized images")
+    return parts, sum(p_.shape[0] for p_ in parts), H, W
+
+
+def conv_tag(kernel: str, width: int, kind: str = "") -> str:
+    """Profiling tag of a convolution launch: ``kernel`` "igemm" / "wgrad", the tile its N dimension of ``width`` channels selects, and
+    the pass.  _lib.CONV_KERNEL_LABEL and profiles/layer_table.py key on these strings."""
+    return f"conv_{kernel}_kernel<{128 if width > 64 else 64}{',' + kind if kind else ''}>"
+
+
 def build_plan(num_keypoints: int, downsample_factor: int) -> Plan:
     """Layer list + flat offsets, parameters in torchvision ``state_dict`` order (backbone first, then head)."""
     if num_keypoints > CPAD:
@@ -151,9 +203,6 @@ def build_plan(num_keypoints: int, downsample_factor: int) -> Plan:
         if c.kind != "stem":
             c.wd_off = wd
             wd += c.numel
-        if c.kind == "convT":
-            c.bias_off = off
-            off += c.Ci
         plan.convs.append(c)
 
     def add_bn(b: BNP):
@@ -174,10 +223,8 @@ def build_plan(num_keypoints: int, downsample_factor: int) -> Plan:
         if blk.down is not None:
             add_conv(blk.down); add_bn(blk.dbn)
     plan.n_backbone = off
-    for c in head:
-        add_conv(c)
-    plan.n_total = off
-    plan.n_wd = wd
+    plan.n_total, plan.n_wd = place_head(head, off, wd)
+    plan.convs += head
     plan.n_running = run
     return plan
 
@@ -190,73 +237,67 @@ class Tape:
         self.meta: dict[str, object] = {}
 
 
-class Engine:
-    # weight gradients on a side stream (measured on the ResNet step: +2 %; on the ViT step, whose main stream is already
-    # MFMA-bound, -8 %, so ViTEngine turns it off)
-    wgrad_side_stream = True
-    dgrad_mask_bits = True
-    bn_bwd_ds = True
-    bn_apply_rbn = True
-    residual_fp32 = False
-    dgrad_half_addend = True
+class EngineCore:
+    """What every executor (Engine, ViTEngine, HeadEngine and their fp32 validation forms) is built on: the flat buffers, the fields
+    the DataParallel wrapper and bench.py drive, the side stream of the weight gradients, the workspaces, and the bf16 head.  Each
+    executor constructs through ``__init__`` here, which sets EVERY field the methods below read - a subclass adds its own after it.
 
-    final_softmax = True   # (HeadEngine: HeatmapHead(final_softmax=False) leaves the last layer's output un-normalised)
+    Of a plan the core needs: ``n_total`` / ``n_wd`` / ``n_running`` (sizes of P, G, Wb / of Wd / of R), ``n_backbone`` (where the head's
+    parameters start), ``head`` and ``convs`` (lists of ConvP with their offsets placed; the head's by ``place_head``) and
+    ``group_ranges()`` (optim.FusedAdam).
 
-    def __init__(self, num_keypoints: int, downsample_factor: int = 2, device: torch.device | str = "cuda:0", plan: Plan | None = None):
+    ``SWITCHES``: the executor's A/B switches as (attribute, environment variable, default), read ONCE, by the constructor - a process
+    that edits the variable after it has built its engine is not followed.  A bool default is switched off by "0" (on by "1" when it is
+    False); a str default keeps the variable's text."""
+
+    SWITCHES: tuple[tuple[str, str, bool | str], ...] = ()
+
+    def __init__(self, plan, num_keypoints: int, downsample_factor: int, device: torch.device | str, final_softmax: bool = True):
         self.device = torch.device(device)
         ops.require_device_type(self.device)
-        _lib.lib()  # fail loudly now if liblp_hip.so is missing
+        self._lib = _lib.lib()  # fail loudly now if liblp_hip.so is missing
         self.K = num_keypoints
         self.ds = downsample_factor
-        self.plan = build_plan(num_keypoints, downsample_factor) if plan is None else plan
+        self.final_softmax = final_softmax   # (HeadEngine: HeatmapHead(final_softmax=False) leaves the last layer's output un-normalised)
+        self.plan = plan
         n = self.plan.n_total
         dev = self.device
         self.P = torch.zeros(n, device=dev, dtype=torch.float32)      # master parameters
         self.G = torch.zeros(n, device=dev, dtype=torch.float32)      # gradients
         self.Wb = torch.zeros(n, device=dev, dtype=torch.bfloat16)    # bf16 operand copy (same offsets)
         self.Wd = torch.zeros(self.plan.n_wd, device=dev, dtype=torch.bfloat16)  # [Ci][R][S][Co] copies for dgrad
-        self.R = torch.zeros(self.plan.n_running, device=dev, dtype=torch.float32)
-        for b in self.plan.bns:
-            self.P[b.g_off:b.g_off + b.C] = 1.0
-            self.R[b.r_off + b.C:b.r_off + 2 * b.C] = 1.0
+        self.R = torch.zeros(self.plan.n_running, device=dev, dtype=torch.float32)   # BatchNorm running statistics (none without a ResNet trunk)
         self.nbt = torch.zeros((), dtype=torch.long)  # shared num_batches_tracked of every BatchNorm
-        self.sync_bn = False          # set by the DDP wrapper when world_size > 1 (reference: train.py:427)
+        self.sync_bn = False          # set by the DDP wrapper when world_size > 1 (reference: train.py:427); without BatchNorm nothing reads it
         # gradient all-reduce overlapped with backward (DataParallel): called with the lowest flat offset whose gradients are FINAL, as the
         # backward pass moves from the head towards the stem; only when the step has ONE backward pass (single_backward: the joint pass
         # of a semi-supervised step, or a supervised step), since two passes accumulate into the same buffer
         self.grad_progress = None
         self.single_backward = False
-        self._bwd_training = True     # mode of the forward pass whose backward is running (eval: no batch-statistics terms)
         self.sync_bn_messages = 0     # SyncBatchNorm all-reduces issued so far (bench.py reports them per step)
         self.process_group = None
-        # SyncBatchNorm transport.  Default: one SUM all-reduce per message.  LP_SYNCBN_GATHER=1: one-shot exchange - every rank's
-        # [segments][2][C] sums are all-gathered (over xGMI each rank writes its 4 - 16 KB straight into every peer's slot: one hop, no
-        # ring) and added locally in RANK ORDER, so every rank holds the same bits whatever the collective's internal order
-        self.sync_bn_gather = os.environ.get("LP_SYNCBN_GATHER", "0") == "1"
-        # lp_bn_bwd_apply in two launches (the correction terms converted by a one-thread-per-value kernel into a small workspace, round 5) or
-        # - LP_BN_BWD_TERMS=0, A/B runs - in the self-contained form that converts them per workgroup into LDS
-        self.bn_bwd_terms = os.environ.get("LP_BN_BWD_TERMS", "1") != "0"
-        self.dgrad_half_addend = os.environ.get("LP_DGRAD_HALF_ADDEND", "1") != "0"   # (0: conv1 first, the shortcut accumulates in place, stand-alone reduction)
-        self.bn_apply_rbn = os.environ.get("LP_BN_APPLY_RBN", "1") != "0"   # (0: the projection shortcut normalised by a pass of its own, lp_bn_apply_seg)
-        self.bn_bwd_ds = os.environ.get("LP_BN_BWD_DS", "1") != "0"   # (0: the projection shortcut's BatchNorm reductions as a pass of their own, lp_bn_bwd_reduce)
-        # The optional "fp32 residual stream" policy (round 6): block outputs that the next block adds as an identity shortcut
-        # are kept as a bf16 pair (hi + lo), a projection shortcut is added unrounded.  NOT the benchmarked default: +3.9 % of the step's HBM time.
-        self.residual_fp32 = os.environ.get("LP_RESIDUAL_FP32", "0") == "1"
-        self.dgrad_mask_bits = os.environ.get("LP_DGRAD_MASK_BITS", "1") != "0"   # (0: the two data gradients into a layer's first block read the bf16 activation as mask)
-        self._gather_buf: torch.Tensor | None = None
-        self._lib = _lib.lib()
         self.profile: list | None = None  # bench.py: [(kernel tag, algorithmic flops, start event, end event)]
         self._wgrad_ws: torch.Tensor | None = None  # split-K partial tiles of the weight-gradient kernels
-        self._red_ws: torch.Tensor | None = None    # per-workgroup rows of the stand-alone BatchNorm reductions
+        self._red_ws: torch.Tensor | None = None    # per-workgroup rows of the stand-alone reductions (BatchNorm, the head's bias sums)
+        # weight gradients on a side stream: only where the executor declares the switch (measured on the ResNet step: +2 %; on the ViT
+        # step, whose main stream is already MFMA-bound, -8 %, so ViTEngine does not)
+        self.wgrad_side_stream = False
         self._side = None                            # side stream of the weight-gradient launches (created on first use)
         self._side_busy = False
         self._side_keep: list = []                   # operands of the side-stream launches in flight (released at the join)
-        self._fold: tuple[torch.Tensor, torch.Tensor] | None = None  # inference copies: BatchNorm folded into (bf16 weights, biases)
+        self._zero_arena: torch.Tensor | None = None   # zeroed reduction targets of the backward pass in flight (_zeros_f32)
+        self._zero_off = 0
+        for attr, var, default in self.SWITCHES:
+            text = os.environ.get(var)
+            if isinstance(default, str):
+                setattr(self, attr, default if text is None else text)
+            else:
+                setattr(self, attr, (text != "0") if default else (text == "1"))
 
     def _zeros_f32(self, n: int) -> torch.Tensor:
-        """n zeroed fp32 words for a reduction target.  Inside backward() they are carved from ONE arena zeroed with a single fill (the
-        step had ~25 separate fills for its BatchNorm / bias sums); outside, an ordinary allocation."""
-        ar = getattr(self, "_zero_arena", None)
+        """n zeroed fp32 words for a reduction target.  Inside Engine.backward() they are carved from ONE arena zeroed with a single fill
+        (the step had ~25 separate fills for its BatchNorm / bias sums); outside, an ordinary allocation."""
+        ar = self._zero_arena
         if ar is not None and self._zero_off + n <= ar.numel():
             t = ar[self._zero_off:self._zero_off + n]
             self._zero_off += (n + 3) // 4 * 4   # (16-B aligned pieces)
@@ -301,8 +342,7 @@ class Engine:
             fn = lambda x_, dy_, g_, dw_, split, ws, nws, st: self._lib.lp_conv_wgrad_bias(x_, dy_, g_, dw_, _p(dbias), split, ws, nws, st)  # noqa: E731
         # (while bench.py's per-launch events are on, the launch stays on the main stream: an event pair there brackets exactly this
         # kernel, as rocprofv3's serialised kernel trace does; on the side stream it would bracket nothing)
-        if (self.device.type != "cuda" or not self.wgrad_side_stream or self.profile is not None
-                or os.environ.get("LP_WGRAD_SIDE_STREAM", "1") == "0"):
+        if self.device.type != "cuda" or not self.wgrad_side_stream or self.profile is not None:
             check(fn(_p(x), _p(dy), C.byref(g), _p(dw), 0, _p(self._wgrad_ws), self._wgrad_ws.numel(), ops._stream()), what)
             return
         if self._side is None:
@@ -320,34 +360,15 @@ class Engine:
         self._side_busy = True
 
     def _join_side_stream(self) -> None:
-        if getattr(self, "_side_busy", False):
+        if self._side_busy:
             torch.cuda.current_stream(self.device).wait_stream(self._side)
             self._side_busy = False
             self._side_keep.clear()  # whatever reuses this memory is enqueued on the main stream behind the wait
 
-    @staticmethod
-    def _bytes(c: "ConvP", g, wgrad: bool = False) -> float:
-        """Algorithmic bytes of one contraction over this layer: the gathered tensor and the other activation-sized operand / result once
-        each (bf16), the weights once (bf16 operand; fp32 for the gradient a weight-gradient launch accumulates into)"""
-        kk = 8 * 8 if c.kind == "stem" else c.k * c.k
-        acts = 2.0 * g.B * (g.Hi * g.Wi * g.Ci + g.Ho * g.Wo * g.Co)
-        return acts + (4.0 if wgrad else 2.0) * c.Co * kk * c.Ci
-
-    @staticmethod
-    def _flops(c: "ConvP", g) -> float:
-        """Algorithmic FLOPs of one contraction over this layer (2 x MACs, logical channels, no padding)."""
-        kk = c.k * c.k
-        if c.kind == "convT":
-            return 2.0 * g.B * g.Ho * g.Wo * c.cin * kk * c.cout
-        return 2.0 * g.B * g.Ho * g.Wo * c.cout * kk * c.cin
-
     # ------------------------------------------------------------------------------------------------ params
-    def param_view(self, c: ConvP | BNP, which: str = "weight", buf: torch.Tensor | None = None) -> torch.Tensor:
-        """torch-shaped (state_dict compatible) view into a flat buffer (parameters by default)."""
+    def param_view(self, c: ConvP, which: str = "weight", buf: torch.Tensor | None = None) -> torch.Tensor:
+        """torch-shaped (state_dict compatible) view of a convolution's weight or bias in a flat buffer (parameters by default)."""
         buf = self.P if buf is None else buf
-        if isinstance(c, BNP):
-            off = c.g_off if which == "weight" else c.b_off
-            return buf[off:off + c.C]
         if which == "bias":
             return buf[c.bias_off:c.bias_off + c.cout]
         flat = buf[c.w_off:c.w_off + c.numel]
@@ -357,38 +378,13 @@ class Engine:
             return flat.view(c.Co, 3, 3, c.Ci)[:c.cin, :, :, :c.cout].permute(0, 3, 1, 2)
         return flat.view(c.Co, c.k, c.k, c.Ci).permute(0, 3, 1, 2)
 
-    def running_view(self, b: BNP, which: str) -> torch.Tensor:
-        off = b.r_off if which == "running_mean" else b.r_off + b.C
-        return self.R[off:off + b.C]
-
-    def state_dict(self) -> dict[str, torch.Tensor]:
-        """Reference-compatible keys/shapes: backbone.{0,1,4..7}.*, head.upsampling_layers.{i}.{weight,bias}."""
-        sd: dict[str, torch.Tensor] = {}
-        plan = self.plan
-
-        def put_bn(b: BNP):
-            sd[f"{b.name}.weight"] = self.param_view(b, "weight")
-            sd[f"{b.name}.bias"] = self.param_view(b, "bias")
-            sd[f"{b.name}.running_mean"] = self.running_view(b, "running_mean")
-            sd[f"{b.name}.running_var"] = self.running_view(b, "running_var")
-            sd[f"{b.name}.num_batches_tracked"] = self.nbt
-
-        sd[f"{plan.stem.name}.weight"] = self.param_view(plan.stem)
-        put_bn(plan.stem_bn)
-        for blk in plan.blocks:
-            for c, b in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3)):
-                sd[f"{c.name}.weight"] = self.param_view(c)
-                put_bn(b)
-            if blk.down is not None:
-                sd[f"{blk.down.name}.weight"] = self.param_view(blk.down)
-                put_bn(blk.dbn)
-        for c in plan.head:
-            sd[f"{c.name}.weight"] = self.param_view(c)
-            sd[f"{c.name}.bias"] = self.param_view(c, "bias")
-        return sd
+    def _head_views(self, buf: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
+        """the head's entries of a state_dict: head.upsampling_layers.{i}.{weight,bias} (the tail of every executor's)"""
+        return {f"{c.name}.{leaf}": self.param_view(c, leaf, buf=buf) for c in self.plan.head for leaf in ("weight", "bias")}
 
     @torch.no_grad()
     def load_state_dict(self, sd: dict[str, torch.Tensor], strict: bool = True) -> None:
+        """Copy the entries of ``sd`` into the views the executor's own ``state_dict()`` names, then refresh the operand copies."""
         own = self.state_dict()
         missing = [k for k in own if k not in sd]
         unexpected = [k for k in sd if k not in own]
@@ -400,16 +396,16 @@ class Engine:
             if k.endswith("num_batches_tracked"):
                 self.nbt.fill_(int(sd[k]))
                 continue
-            dst.copy_(sd[k].to(device=self.device, dtype=torch.float32))
+            dst.copy_(sd[k].to(device=self.device, dtype=torch.float32).reshape(dst.shape))
         self.refresh_weight_copies()
 
     def invalidate_inference_copies(self) -> None:
-        """Parameters or running statistics changed: the folded inference weights are rebuilt on the next forward_infer()."""
-        self._fold = None
+        """Parameters (or running statistics) changed.  Nothing here is derived from them beyond the operand copies; Engine drops its
+        folded inference weights."""
 
     def refresh_weight_copies(self, lo: int = 0, hi: int | None = None) -> None:
         """bf16 operand copy of P[lo:hi] and the transposed copies of the conv weights inside that range."""
-        self._fold = None
+        self.invalidate_inference_copies()
         hi = self.plan.n_total if hi is None else hi
         check(self._lib.lp_cast_bf16(_p(self.P[lo:hi]), hi - lo, _p(self.Wb[lo:hi]), ops._stream()), "lp_cast_bf16")
         self.refresh_dgrad_copies(lo, hi)
@@ -436,143 +432,9 @@ class Engine:
     def _reduce_ws(self, M: int, C_: int) -> torch.Tensor:
         """Scratch rows of the stand-alone reductions (lp_bn_stats, lp_bn_bwd_reduce): one buffer, reused in stream order"""
         need = int(self._lib.lp_bn_reduce_workspace_bytes(M, C_))
-        if getattr(self, "_red_ws", None) is None or self._red_ws.numel() < need:   # (ViTEngine shares the head code with its own __init__)
+        if self._red_ws is None or self._red_ws.numel() < need:
             self._red_ws = torch.empty(max(need, 4 << 20), device=self.device, dtype=torch.uint8)
         return self._red_ws
-
-    def _bn_fuse(self, sums: torch.Tensor, b: BNP | None = None, z=None, mean=None, invstd=None, mask_from_z: bool = False,
-                 relu_bits=None, seg: int = 0, addend_half: bool = False) -> _lib.BnFuse:
-        """lp_bn_fuse for one launch: ``sums`` alone = the forward form ([sum z, sum z^2] of the output); with ``b`` / ``z`` / ``mean`` /
-        ``invstd`` the backward form ([sum dz, sum dz * xhat] of the gradient the launch produces)."""
-        f = _lib.BnFuse()
-        f.addend_half = int(addend_half)
-        f.sums = sums.data_ptr()
-        f.seg_images = seg
-        if b is not None:
-            f.z, f.mean, f.invstd = z.data_ptr(), mean.data_ptr(), invstd.data_ptr()
-            f.gamma, f.beta = self.param_view(b, "weight").data_ptr(), self.param_view(b, "bias").data_ptr()
-            f.mask_from_z = int(mask_from_z)
-            f.relu_bits = relu_bits.data_ptr() if relu_bits is not None else None
-        return f
-
-    def _conv_fwd(self, c: ConvP, x: torch.Tensor, B: int, Hi: int, Wi: int, sums: torch.Tensor | None = None, seg: int = 0):
-        """``sums`` (segments,2,Co) fixed point: also accumulate [sum z, sum z^2] of the output there (the next BatchNorm's statistics
-        pass, fused); ``seg`` > 0: images [0, seg) and [seg, B) are two BatchNorm segments with their own sums."""
-        g = self._geom(c, B, Hi, Wi)
-        out = torch.empty(B, g.Ho, g.Wo, c.Co, device=self.device, dtype=torch.bfloat16)
-        w = self.Wb[c.w_off:]
-        st = ops._stream()
-        if c.kind == "stem":
-            if sums is None:
-                run = lambda: check(self._lib.lp_stem_fwd(_p(x), _p(w), C.byref(g), _p(out), st), "lp_stem_fwd")  # noqa: E731
-            else:
-                f = self._bn_fuse(sums, seg=seg)
-                run = lambda: check(self._lib.lp_stem_fwd_bn(_p(x), _p(w), C.byref(g), _p(out), C.byref(f), st), "lp_stem_fwd_bn")  # noqa: E731
-            self._timed("conv_igemm_kernel<64,stem>", self._flops(c, g), run, self._bytes(c, g), layer=c.name)
-        else:
-            if sums is None:
-                run = lambda: check(self._lib.lp_conv_fwd(_p(x), _p(w), C.byref(g), None, _p(out), None, c.Co, 0, st), "lp_conv_fwd")  # noqa: E731
-            else:
-                f = self._bn_fuse(sums, seg=seg)
-                run = lambda: check(self._lib.lp_conv_fwd_bn(_p(x), _p(w), C.byref(g), _p(out), C.byref(f), st), "lp_conv_fwd_bn")  # noqa: E731
-            self._timed(f"conv_igemm_kernel<{128 if c.Co > 64 else 64},fwd>", self._flops(c, g), run, self._bytes(c, g), layer=c.name)
-        return out, g
-
-    @staticmethod
-    def _segments(B: int, seg: int) -> list[tuple[int, int]]:
-        """[(first image, images)] of the BatchNorm segments of a pass over B images"""
-        return [(0, B)] if not seg else [(0, seg), (seg, B - seg)]
-
-    def can_segment(self, n0: int, H: int, W: int) -> bool:
-        """Can a pass over n0 + n1 images of H x W keep two BatchNorm segments in ONE launch per layer?  The segment boundary must
-        fall on a 128-row tile boundary of every fused launch; the smallest per-image row count (the trunk's output map, which is also
-        what a parity class of the stride-2 data gradients covers) decides, every other map is 4^k times larger."""
-        return n0 > 0 and H % 32 == 0 and W % 32 == 0 and (n0 * (H // 32) * (W // 32)) % 128 == 0
-
-    def _sync_stats(self, t: torch.Tensor) -> None:
-        """SUM of one SyncBatchNorm message ((segments, 2, C) fixed-point sums = int64 words) over the ranks, in place (reference:
-        ``sync_batchnorm=True``, train.py:427).  Integer sums: every rank ends with the same bits whatever order the collective adds in.
-        An all-reduce, or - LP_SYNCBN_GATHER=1 - the one-shot form: all-gather the ranks' messages, add the rows locally."""
-        if self.sync_bn_gather:
-            if not t.is_contiguous():
-                raise ValueError("a SyncBatchNorm message must be a contiguous buffer (the sum is written back through it)")
-            world, n = dist.get_world_size(self.process_group), t.numel()
-            if self._gather_buf is None or self._gather_buf.numel() < world * n:   # sized once for the widest layer, two segments
-                widest = max([2 * b.C for b in self.plan.bns] + [2 * self.plan.stem_bn.C]) * 2 * 2
-                self._gather_buf = torch.empty(world * max(n, widest), device=t.device, dtype=t.dtype)
-            flat = self._gather_buf[:world * n]
-            dist.all_gather_into_tensor(flat, t.reshape(-1), group=self.process_group)   # (flat output: the form gloo and RCCL both take)
-            torch.sum(flat.view(world, n), dim=0, out=t.view(-1))
-        else:
-            dist.all_reduce(t, group=self.process_group)
-
-    def _bn_moments(self, b: BNP, z: torch.Tensor, M: int, training: bool, sums: torch.Tensor, have_sums: bool = False, seg: int = 0):
-        """-> (mean, invstd) of this pass, each (segments, C) flattened: batch statistics (running statistics updated, segment by
-        segment) in training, running statistics otherwise"""
-        B = z.shape[0]
-        rpi = M // B
-        segs = self._segments(B, seg if training else 0)
-        mean = torch.empty(len(segs) * b.C, device=self.device, dtype=torch.float32)
-        invstd = torch.empty_like(mean)
-        if training:
-            if not have_sums:
-                rws = self._reduce_ws(M, b.C)
-                for si, (i0, n) in enumerate(segs):
-                    check(self._lib.lp_bn_stats(_p(z[i0:i0 + n]), n * rpi, b.C, _p(sums[si * 4 * b.C:]), _p(rws), rws.numel(), ops._stream()),
-                          "lp_bn_stats")
-            counts = [float(n * rpi) for _, n in segs]
-            if self.sync_bn:  # ONE message carries every segment's [sum, sum of squares]
-                self._sync_stats(sums)
-                self.sync_bn_messages += 1
-                counts = [c_ * dist.get_world_size(self.process_group) for c_ in counts]
-            rm, rv = _p(self.running_view(b, "running_mean")), _p(self.running_view(b, "running_var"))
-            if len(segs) == 1:
-                check(self._lib.lp_bn_finalize(_p(sums), counts[0], b.C, BN_EPS, BN_MOMENTUM, _p(mean), _p(invstd), rm, rv, ops._stream()),
-                      "lp_bn_finalize")
-            else:
-                check(self._lib.lp_bn_finalize2(_p(sums), counts[0], counts[1], b.C, BN_EPS, BN_MOMENTUM, _p(mean), _p(invstd), rm, rv,
-                                                ops._stream()), "lp_bn_finalize2")
-        else:
-            mean.copy_(self.running_view(b, "running_mean"))
-            invstd.copy_((self.running_view(b, "running_var") + BN_EPS).rsqrt())
-        return mean, invstd
-
-    def _bn_fwd(self, b: BNP, z: torch.Tensor, M: int, residual: torch.Tensor | None, relu: bool, training: bool, sums: torch.Tensor,
-                have_sums: bool = False, want_bits: bool = False, seg: int = 0, residual_bn=None, pair=None):
-        """-> (y, mean, invstd[, relu_bits]); ``want_bits``: also the 1-bit ReLU mask (M*C/8 bytes) for the backward pass.
-        ``residual_bn`` = (BNP, mean_d, invstd_d): ``residual`` is the PRE-normalisation tensor of the block's projection shortcut, normalised
-        inside this pass (lp_bn_apply_seg_rbn) instead of by a pass of its own that writes the normalised shortcut and this one reads back."""
-        mean, invstd = self._bn_moments(b, z, M, training, sums, have_sums, seg)
-        y = torch.empty_like(z)
-        bits = torch.empty(M * b.C // 8, device=self.device, dtype=torch.uint8) if want_bits else None
-        B = z.shape[0]
-        rpi = M // B
-        gam, bet = _p(self.param_view(b, "weight")), _p(self.param_view(b, "bias"))
-        # both segments in ONE launch (the kernel walks each segment with that segment's terms in registers)
-        if pair is not None:
-            # fp32-residual policy: ``pair`` = (residual_lo or None, y_lo or None): lp_bn_apply_seg_lo adds hi + lo (or the unrounded
-            # normalised shortcut) and leaves this output's own lo word for the next identity block
-            res_lo, y_lo = pair
-            if residual_bn is not None:
-                bd, md, vd = residual_bn
-                check(self._lib.lp_bn_apply_seg_lo(_p(z), _p(mean), _p(invstd), gam, bet, None, None, _p(residual), _p(md), _p(vd),
-                                                   _p(self.param_view(bd, "weight")), _p(self.param_view(bd, "bias")), int(relu), M, b.C,
-                                                   (seg if training else 0) * rpi, _p(y), _p(y_lo), _p(bits), ops._stream()), "lp_bn_apply_seg_lo")
-            else:
-                check(self._lib.lp_bn_apply_seg_lo(_p(z), _p(mean), _p(invstd), gam, bet, _p(residual), _p(res_lo), None, None, None, None, None,
-                                                   int(relu), M, b.C, (seg if training else 0) * rpi, _p(y), _p(y_lo), _p(bits), ops._stream()),
-                      "lp_bn_apply_seg_lo")
-        elif residual_bn is not None:
-            bd, md, vd = residual_bn
-            check(self._lib.lp_bn_apply_seg_rbn(_p(z), _p(mean), _p(invstd), gam, bet, _p(residual), _p(md), _p(vd), _p(self.param_view(bd, "weight")),
-                                                _p(self.param_view(bd, "bias")), int(relu), M, b.C, (seg if training else 0) * rpi, _p(y), _p(bits),
-                                                ops._stream()), "lp_bn_apply_seg_rbn")
-        else:
-            check(self._lib.lp_bn_apply_seg(_p(z), _p(mean), _p(invstd), gam, bet, _p(residual), int(relu), M, b.C,
-                                            (seg if training else 0) * rpi, _p(y), _p(bits), ops._stream()), "lp_bn_apply_seg")
-        if want_bits:
-            return y, mean, invstd, bits
-        return y, mean, invstd
 
     # ------------------------------------------------------------------------------------------------ head
     def _head_forward(self, x: torch.Tensor, B: int, h: int, w: int, T: dict) -> torch.Tensor:
@@ -648,6 +510,228 @@ class Engine:
         check(self._lib.lp_pixel_shuffle(_p(dcur), B, fh, fw, cs, ld, 1, _p(d), ops._stream()), "lp_pixel_shuffle(inv)")
         return d
 
+
+class Engine(EngineCore):
+    """The ResNet-50 trunk + head (the module docstring's design): the core plus BatchNorm, the fused trunk passes and the folded
+    inference copies."""
+
+    SWITCHES = (
+        ("wgrad_side_stream", "LP_WGRAD_SIDE_STREAM", True),
+        # SyncBatchNorm transport.  Default: one SUM all-reduce per message.  LP_SYNCBN_GATHER=1: one-shot exchange - every rank's
+        # [segments][2][C] sums are all-gathered (over xGMI each rank writes its 4 - 16 KB straight into every peer's slot: one hop, no
+        # ring) and added locally in RANK ORDER, so every rank holds the same bits whatever the collective's internal order
+        ("sync_bn_gather", "LP_SYNCBN_GATHER", False),
+        # lp_bn_bwd_apply in two launches (the correction terms converted by a one-thread-per-value kernel into a small workspace, round 5) or
+        # - LP_BN_BWD_TERMS=0, A/B runs - in the self-contained form that converts them per workgroup into LDS
+        ("bn_bwd_terms", "LP_BN_BWD_TERMS", True),
+        ("dgrad_half_addend", "LP_DGRAD_HALF_ADDEND", True),   # (0: conv1 first, the shortcut accumulates in place, stand-alone reduction)
+        ("bn_apply_rbn", "LP_BN_APPLY_RBN", True),   # (0: the projection shortcut normalised by a pass of its own, lp_bn_apply_seg)
+        ("bn_bwd_ds", "LP_BN_BWD_DS", True),   # (0: the projection shortcut's BatchNorm reductions as a pass of their own, lp_bn_bwd_reduce)
+        # The optional "fp32 residual stream" policy (round 6, DESIGN.md section 3): block outputs that the next block adds as an identity shortcut
+        # are kept as a bf16 pair (hi + lo), a projection shortcut is added unrounded.  NOT the benchmarked default: +3.9 % of the step's HBM time.
+        ("residual_fp32", "LP_RESIDUAL_FP32", False),
+        ("dgrad_mask_bits", "LP_DGRAD_MASK_BITS", True),   # (0: the two data gradients into a layer's first block read the bf16 activation as mask)
+    )
+
+    def __init__(self, num_keypoints: int, downsample_factor: int = 2, device: torch.device | str = "cuda:0"):
+        super().__init__(build_plan(num_keypoints, downsample_factor), num_keypoints, downsample_factor, device)
+        for b in self.plan.bns:
+            self.P[b.g_off:b.g_off + b.C] = 1.0
+            self.R[b.r_off + b.C:b.r_off + 2 * b.C] = 1.0
+        self._bwd_training = True     # mode of the forward pass whose backward is running (eval: no batch-statistics terms)
+        self._gather_buf: torch.Tensor | None = None   # LP_SYNCBN_GATHER=1: the ranks' messages side by side
+        self._ds_ws: torch.Tensor | None = None     # scratch of lp_bn_bwd_apply_seg_ds
+        self._fold: tuple[torch.Tensor, torch.Tensor] | None = None  # inference copies: BatchNorm folded into (bf16 weights, biases)
+
+    @staticmethod
+    def _bytes(c: "ConvP", g, wgrad: bool = False) -> float:
+        """Algorithmic bytes of one contraction over this layer: the gathered tensor and the other activation-sized operand / result once
+        each (bf16), the weights once (bf16 operand; fp32 for the gradient a weight-gradient launch accumulates into)"""
+        kk = 8 * 8 if c.kind == "stem" else c.k * c.k
+        acts = 2.0 * g.B * (g.Hi * g.Wi * g.Ci + g.Ho * g.Wo * g.Co)
+        return acts + (4.0 if wgrad else 2.0) * c.Co * kk * c.Ci
+
+    @staticmethod
+    def _flops(c: "ConvP", g) -> float:
+        """Algorithmic FLOPs of one contraction over this layer (2 x MACs, logical channels, no padding)."""
+        kk = c.k * c.k
+        if c.kind == "convT":
+            return 2.0 * g.B * g.Ho * g.Wo * c.cin * kk * c.cout
+        return 2.0 * g.B * g.Ho * g.Wo * c.cout * kk * c.cin
+
+    # ------------------------------------------------------------------------------------------------ params
+    def param_view(self, c: ConvP | BNP, which: str = "weight", buf: torch.Tensor | None = None) -> torch.Tensor:
+        """the core's view of a convolution, or a BatchNorm's scale / shift"""
+        if not isinstance(c, BNP):
+            return EngineCore.param_view(self, c, which, buf)
+        buf = self.P if buf is None else buf
+        off = c.g_off if which == "weight" else c.b_off
+        return buf[off:off + c.C]
+
+    def running_view(self, b: BNP, which: str) -> torch.Tensor:
+        off = b.r_off if which == "running_mean" else b.r_off + b.C
+        return self.R[off:off + b.C]
+
+    def invalidate_inference_copies(self) -> None:
+        """Parameters or running statistics changed: the folded inference weights are rebuilt on the next forward_infer()."""
+        self._fold = None
+
+    def state_dict(self) -> dict[str, torch.Tensor]:
+        """Reference-compatible keys/shapes: backbone.{0,1,4..7}.*, head.upsampling_layers.{i}.{weight,bias}."""
+        sd: dict[str, torch.Tensor] = {}
+        plan = self.plan
+
+        def put_bn(b: BNP):
+            sd[f"{b.name}.weight"] = self.param_view(b, "weight")
+            sd[f"{b.name}.bias"] = self.param_view(b, "bias")
+            sd[f"{b.name}.running_mean"] = self.running_view(b, "running_mean")
+            sd[f"{b.name}.running_var"] = self.running_view(b, "running_var")
+            sd[f"{b.name}.num_batches_tracked"] = self.nbt
+
+        sd[f"{plan.stem.name}.weight"] = self.param_view(plan.stem)
+        put_bn(plan.stem_bn)
+        for blk in plan.blocks:
+            for c, b in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3)):
+                sd[f"{c.name}.weight"] = self.param_view(c)
+                put_bn(b)
+            if blk.down is not None:
+                sd[f"{blk.down.name}.weight"] = self.param_view(blk.down)
+                put_bn(blk.dbn)
+        sd.update(self._head_views())
+        return sd
+
+    def _bn_fuse(self, sums: torch.Tensor, b: BNP | None = None, z=None, mean=None, invstd=None, mask_from_z: bool = False,
+                 relu_bits=None, seg: int = 0, addend_half: bool = False) -> _lib.BnFuse:
+        """lp_bn_fuse for one launch: ``sums`` alone = the forward form ([sum z, sum z^2] of the output); with ``b`` / ``z`` / ``mean`` /
+        ``invstd`` the backward form ([sum dz, sum dz * xhat] of the gradient the launch produces)."""
+        f = _lib.BnFuse()
+        f.addend_half = int(addend_half)
+        f.sums = sums.data_ptr()
+        f.seg_images = seg
+        if b is not None:
+            f.z, f.mean, f.invstd = z.data_ptr(), mean.data_ptr(), invstd.data_ptr()
+            f.gamma, f.beta = self.param_view(b, "weight").data_ptr(), self.param_view(b, "bias").data_ptr()
+            f.mask_from_z = int(mask_from_z)
+            f.relu_bits = relu_bits.data_ptr() if relu_bits is not None else None
+        return f
+
+    def _conv_fwd(self, c: ConvP, x: torch.Tensor, B: int, Hi: int, Wi: int, sums: torch.Tensor | None = None, seg: int = 0):
+        """``sums`` (segments,2,Co) fixed point: also accumulate [sum z, sum z^2] of the output there (the next BatchNorm's statistics
+        pass, fused); ``seg`` > 0: images [0, seg) and [seg, B) are two BatchNorm segments with their own sums."""
+        g = self._geom(c, B, Hi, Wi)
+        out = torch.empty(B, g.Ho, g.Wo, c.Co, device=self.device, dtype=torch.bfloat16)
+        w = self.Wb[c.w_off:]
+        st = ops._stream()
+        if c.kind == "stem":
+            if sums is None:
+                run = lambda: check(self._lib.lp_stem_fwd(_p(x), _p(w), C.byref(g), _p(out), st), "lp_stem_fwd")  # noqa: E731
+            else:
+                f = self._bn_fuse(sums, seg=seg)
+                run = lambda: check(self._lib.lp_stem_fwd_bn(_p(x), _p(w), C.byref(g), _p(out), C.byref(f), st), "lp_stem_fwd_bn")  # noqa: E731
+            self._timed(conv_tag("igemm", 64, "stem"), self._flops(c, g), run, self._bytes(c, g), layer=c.name)
+        else:
+            if sums is None:
+                run = lambda: check(self._lib.lp_conv_fwd(_p(x), _p(w), C.byref(g), None, _p(out), None, c.Co, 0, st), "lp_conv_fwd")  # noqa: E731
+            else:
+                f = self._bn_fuse(sums, seg=seg)
+                run = lambda: check(self._lib.lp_conv_fwd_bn(_p(x), _p(w), C.byref(g), _p(out), C.byref(f), st), "lp_conv_fwd_bn")  # noqa: E731
+            self._timed(conv_tag("igemm", c.Co, "fwd"), self._flops(c, g), run, self._bytes(c, g), layer=c.name)
+        return out, g
+
+    @staticmethod
+    def _segments(B: int, seg: int) -> list[tuple[int, int]]:
+        """[(first image, images)] of the BatchNorm segments of a pass over B images"""
+        return [(0, B)] if not seg else [(0, seg), (seg, B - seg)]
+
+    def can_segment(self, n0: int, H: int, W: int) -> bool:
+        """Can a pass over n0 + n1 images of H x W keep two BatchNorm segments in ONE launch per layer?  The segment boundary must
+        fall on a 128-row tile boundary of every fused launch; the smallest per-image row count (the trunk's output map, which is also
+        what a parity class of the stride-2 data gradients covers) decides, every other map is 4^k times larger."""
+        return n0 > 0 and H % 32 == 0 and W % 32 == 0 and (n0 * (H // 32) * (W // 32)) % 128 == 0
+
+    def _sync_stats(self, t: torch.Tensor) -> None:
+        """SUM of one SyncBatchNorm message ((segments, 2, C) fixed-point sums = int64 words) over the ranks, in place (reference:
+        ``sync_batchnorm=True``, train.py:427).  Integer sums: every rank ends with the same bits whatever order the collective adds in.
+        An all-reduce, or - LP_SYNCBN_GATHER=1 - the one-shot form: all-gather the ranks' messages, add the rows locally."""
+        if self.sync_bn_gather:
+            if not t.is_contiguous():
+                raise ValueError("a SyncBatchNorm message must be a contiguous buffer (the sum is written back through it)")
+            world, n = dist.get_world_size(self.process_group), t.numel()
+            if self._gather_buf is None or self._gather_buf.numel() < world * n:   # sized once for the widest layer, two segments
+                widest = max([2 * b.C for b in self.plan.bns] + [2 * self.plan.stem_bn.C]) * 2 * 2
+                self._gather_buf = torch.empty(world * max(n, widest), device=t.device, dtype=t.dtype)
+            flat = self._gather_buf[:world * n]
+            dist.all_gather_into_tensor(flat, t.reshape(-1), group=self.process_group)   # (flat output: the form gloo and RCCL both take)
+            torch.sum(flat.view(world, n), dim=0, out=t.view(-1))
+        else:
+            dist.all_reduce(t, group=self.process_group)
+
+    def _bn_moments(self, b: BNP, z: torch.Tensor, M: int, training: bool, sums: torch.Tensor, have_sums: bool = False, seg: int = 0):
+        """-> (mean, invstd) of this pass, each (segments, C) flattened: batch statistics (running statistics updated, segment by
+        segment) in training, running statistics otherwise"""
+        B = z.shape[0]
+        rpi = M // B
+        segs = self._segments(B, seg if training else 0)
+        mean = torch.empty(len(segs) * b.C, device=self.device, dtype=torch.float32)
+        invstd = torch.empty_like(mean)
+        if training:
+            if not have_sums:
+                rws = self._reduce_ws(M, b.C)
+                for si, (i0, n) in enumerate(segs):
+                    check(self._lib.lp_bn_stats(_p(z[i0:i0 + n]), n * rpi, b.C, _p(sums[si * 4 * b.C:]), _p(rws), rws.numel(), ops._stream()),
+                          "lp_bn_stats")
+            counts = [float(n * rpi) for _, n in segs]
+            if self.sync_bn:  # ONE message carries every segment's [sum, sum of squares]
+                self._sync_stats(sums)
+                self.sync_bn_messages += 1
+                counts = [c_ * dist.get_world_size(self.process_group) for c_ in counts]
+            rm, rv = _p(self.running_view(b, "running_mean")), _p(self.running_view(b, "running_var"))
+            if len(segs) == 1:
+                check(self._lib.lp_bn_finalize(_p(sums), counts[0], b.C, BN_EPS, BN_MOMENTUM, _p(mean), _p(invstd), rm, rv, ops._stream()),
+                      "lp_bn_finalize")
+            else:
+                check(self._lib.lp_bn_finalize2(_p(sums), counts[0], counts[1], b.C, BN_EPS, BN_MOMENTUM, _p(mean), _p(invstd), rm, rv,
+                                                ops._stream()), "lp_bn_finalize2")
+        else:
+            mean.copy_(self.running_view(b, "running_mean"))
+            invstd.copy_((self.running_view(b, "running_var") + BN_EPS).rsqrt())
+        return mean, invstd
+
+    def _bn_fwd(self, b: BNP, z: torch.Tensor, M: int, residual: torch.Tensor | None, relu: bool, training: bool, sums: torch.Tensor,
+                have_sums: bool = False, want_bits: bool = False, seg: int = 0, residual_bn=None, pair=None):
+        """-> (y, mean, invstd, relu_bits); ``want_bits``: relu_bits is the 1-bit ReLU mask (M*C/8 bytes) for the backward pass, else None.
+        ``residual_bn`` = (BNP, mean_d, invstd_d): ``residual`` is the PRE-normalisation tensor of the block's projection shortcut, normalised
+        inside this pass (lp_bn_apply_seg_rbn) instead of by a pass of its own that writes the normalised shortcut and this one reads back."""
+        mean, invstd = self._bn_moments(b, z, M, training, sums, have_sums, seg)
+        y = torch.empty_like(z)
+        bits = torch.empty(M * b.C // 8, device=self.device, dtype=torch.uint8) if want_bits else None
+        B = z.shape[0]
+        rpi = M // B
+        gam, bet = _p(self.param_view(b, "weight")), _p(self.param_view(b, "bias"))
+        # both segments in ONE launch (the kernel walks each segment with that segment's terms in registers)
+        if pair is not None:
+            # fp32-residual policy: ``pair`` = (residual_lo or None, y_lo or None): lp_bn_apply_seg_lo adds hi + lo (or the unrounded
+            # normalised shortcut) and leaves this output's own lo word for the next identity block
+            res_lo, y_lo = pair
+            if residual_bn is not None:
+                bd, md, vd = residual_bn
+                check(self._lib.lp_bn_apply_seg_lo(_p(z), _p(mean), _p(invstd), gam, bet, None, None, _p(residual), _p(md), _p(vd),
+                                                   _p(self.param_view(bd, "weight")), _p(self.param_view(bd, "bias")), int(relu), M, b.C,
+                                                   (seg if training else 0) * rpi, _p(y), _p(y_lo), _p(bits), ops._stream()), "lp_bn_apply_seg_lo")
+            else:
+                check(self._lib.lp_bn_apply_seg_lo(_p(z), _p(mean), _p(invstd), gam, bet, _p(residual), _p(res_lo), None, None, None, None, None,
+                                                   int(relu), M, b.C, (seg if training else 0) * rpi, _p(y), _p(y_lo), _p(bits), ops._stream()),
+                      "lp_bn_apply_seg_lo")
+        elif residual_bn is not None:
+            bd, md, vd = residual_bn
+            check(self._lib.lp_bn_apply_seg_rbn(_p(z), _p(mean), _p(invstd), gam, bet, _p(residual), _p(md), _p(vd), _p(self.param_view(bd, "weight")),
+                                                _p(self.param_view(bd, "bias")), int(relu), M, b.C, (seg if training else 0) * rpi, _p(y), _p(bits),
+                                                ops._stream()), "lp_bn_apply_seg_rbn")
+        else:
+            check(self._lib.lp_bn_apply_seg(_p(z), _p(mean), _p(invstd), gam, bet, _p(residual), int(relu), M, b.C,
+                                            (seg if training else 0) * rpi, _p(y), _p(bits), ops._stream()), "lp_bn_apply_seg")
+        return y, mean, invstd, bits
+
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, images, training: bool = True) -> tuple[torch.Tensor, Tape]:
         """images (B,3,H,W) fp32 NCHW -> heat-maps (B,K,H/2^ds,W/2^ds) fp32, plus the tape for backward().
@@ -656,18 +740,7 @@ class Engine:
         models/base.py:682-695): both go through every layer in ONE launch, as two BatchNorm segments that keep their own batch
         statistics and update the running statistics in order - the result of the reference's two forward calls at the launch count
         and tile fill of one (check ``can_segment`` first)."""
-        parts = list(images) if isinstance(images, (list, tuple)) else [images]
-        for p_ in parts:
-            ops.require_device(p_)
-        parts = [p_.to(torch.float32).contiguous() for p_ in parts]
-        if parts[0].dim() != 4 or parts[0].shape[1] != 3:
-            raise ValueError(f"images must be (B, 3, H, W), got {tuple(parts[0].shape)}")   # (raw pointers from here on)
-        _, _, H, W = parts[0].shape
-        if H % 32 or W % 32:
-            raise ValueError(f"image size must be a multiple of 32, got {H}x{W}")
-        if len(parts) > 2 or any(p_.shape[1:] != parts[0].shape[1:] for p_ in parts):
-            raise ValueError("a joint pass takes at most two batches of equally sized images")
-        B = sum(p_.shape[0] for p_ in parts)
+        parts, B, H, W = image_parts(images, 32, 2)
         seg = parts[0].shape[0] if (len(parts) == 2 and training) else 0
         if seg and not self.can_segment(seg, H, W):
             raise NotImplementedError(f"{seg} images of {H}x{W} do not end on a tile boundary in every layer: run the two batches separately")
@@ -700,11 +773,10 @@ class Engine:
             if not apply:
                 mm, vv = self._bn_moments(b, zz, B * gg.Ho * gg.Wo, training, sums, training, seg)
                 return zz, None, mm, vv, gg
-            res = self._bn_fwd(b, zz, B * gg.Ho * gg.Wo, residual, relu, training, sums, have_sums=training,
-                               want_bits=bits_key is not None and training, seg=seg, residual_bn=residual_bn, pair=pair)
-            if len(res) == 4:
-                T[bits_key] = res[3]
-            aa, mm, vv = res[:3]
+            aa, mm, vv, bits = self._bn_fwd(b, zz, B * gg.Ho * gg.Wo, residual, relu, training, sums, have_sums=training,
+                                            want_bits=bits_key is not None and training, seg=seg, residual_bn=residual_bn, pair=pair)
+            if bits is not None:
+                T[bits_key] = bits
             return zz, aa, mm, vv, gg
 
         # stem: conv -> [BatchNorm -> ReLU -> max-pool] in one pass; the full-resolution activation between them is never stored
@@ -789,13 +861,7 @@ class Engine:
         """Inference forward (predict_step, reference models/heatmap_tracker.py:155-191, with eval-mode BatchNorm): every
         conv -> BatchNorm [-> + identity] [-> ReLU] of the trunk is ONE launch on folded weights (lp_conv_fwd_act); no BatchNorm
         passes, no pre-normalisation tensors, no tape.  images (B,3,H,W) fp32 -> heat-maps (B,K,H/2^ds,W/2^ds) fp32."""
-        ops.require_device(images)
-        images = images.to(torch.float32).contiguous()
-        if images.dim() != 4 or images.shape[1] != 3:
-            raise ValueError(f"images must be (B, 3, H, W), got {tuple(images.shape)}")
-        B, _, H, W = images.shape
-        if H % 32 or W % 32:
-            raise ValueError(f"image size must be a multiple of 32, got {H}x{W}")
+        (images,), B, H, W = image_parts(images, 32, 1)
         plan = self.plan
         wf, bf = self._folded()
         st = ops._stream()
@@ -819,7 +885,7 @@ class Engine:
             out = torch.empty(B, g_.Ho, g_.Wo, c.Co, device=self.device, dtype=torch.bfloat16)
             run = lambda: check(self._lib.lp_conv_fwd_act(_p(xin), _p(wf[c.w_off:]), C.byref(g_), _p(bf[b.b_off:]), _p(residual), int(relu),  # noqa: E731
                                                           _p(out), st), "lp_conv_fwd_act")
-            self._timed(f"conv_igemm_kernel<{128 if c.Co > 64 else 64},infer>", self._flops(c, g_), run, self._bytes(c, g_), layer=c.name)
+            self._timed(conv_tag("igemm", c.Co, "infer"), self._flops(c, g_), run, self._bytes(c, g_), layer=c.name)
             return out, g_
 
         for blk in plan.blocks:
@@ -832,10 +898,11 @@ class Engine:
 
     # ------------------------------------------------------------------------------------------------ backward
     def _bn_bwd(self, b: BNP, dy, y_out, z, mean, invstd, M: int, want_dres: bool, sums: torch.Tensor | None = None, seg: int = 0, ds=None):
-        """``sums``: the (segments,2,C) fixed-point reductions [sum dy, sum dy*xhat] when the dgrad that produced ``dy`` already made them.
+        """-> (dz, dres or None, dsums or None).
+        ``sums``: the (segments,2,C) fixed-point reductions [sum dy, sum dy*xhat] when the dgrad that produced ``dy`` already made them.
         The apply launch also adds THIS rank's sums into d beta / d gamma (they are the parameter gradients).
         ``ds`` = (zd, mean_d, invstd_d) of the block's projection-shortcut BatchNorm, which the same (masked) gradient feeds: the walk then
-        also leaves THAT BatchNorm's two reductions - returned as a third value, or None where the library declines (the caller then runs
+        also leaves THAT BatchNorm's two reductions - ``dsums``; None without ``ds`` or where the library declines (the caller then runs
         lp_bn_bwd_reduce as before) - instead of a separate pass over the gradient (lp_bn_bwd_apply_seg_ds)."""
         B = z.shape[0]
         rpi = M // B
@@ -871,7 +938,7 @@ class Engine:
                 zd, md, vd = ds
                 dsums = self._zeros_fx(len(segs) * 2 * Cn)
                 need = int(self._lib.lp_bn_bwd_ds_workspace_bytes(M, Cn))
-                if getattr(self, "_ds_ws", None) is None or self._ds_ws.numel() < need:
+                if self._ds_ws is None or self._ds_ws.numel() < need:
                     self._ds_ws = torch.empty(need, device=self.device, dtype=torch.uint8)
                 check(self._lib.lp_bn_bwd_apply_seg_ds(_p(dy), _p(y_out), _p(z), _p(mean), _p(invstd), gam, _p(total), counts[0], counts[-1], M, Cn,
                                                        seg * rpi, _p(dz), _p(dres), _p(local), _p(self.G[b.b_off:]), _p(self.G[b.g_off:]),
@@ -881,7 +948,7 @@ class Engine:
         check(self._lib.lp_bn_bwd_apply_seg(_p(dy), _p(y_out), _p(z), _p(mean), _p(invstd), gam, _p(total), counts[0], counts[-1], M, Cn,
                                             seg * rpi, _p(dz), _p(dres), _p(local), _p(self.G[b.b_off:]), _p(self.G[b.g_off:]), _p(terms),
                                             ops._stream()), "lp_bn_bwd_apply_seg")
-        return (dz, dres, None) if ds is not None else (dz, dres)
+        return dz, dres, None
 
     def _conv_bwd(self, c: ConvP, x, dz, B, Hi, Wi, need_dx: bool, addend=None, relu_mask=None, accumulate_into=None, bn=None,
                   relu_bits=None, seg: int = 0, mask_bits=None, addend_half: bool = False):
@@ -893,7 +960,7 @@ class Engine:
         g = self._geom(c, B, Hi, Wi)
         # (the weight gradient is enqueued BEFORE the layer's data gradient: the side stream starts it at once, beside the data gradient.  Enqueued
         # behind it - so that it would run beside the HBM-bound BatchNorm kernels instead - the step was 1.3 % slower, profiles/r05o_wgrad_order_ab.txt)
-        self._timed(f"conv_wgrad_kernel<{128 if c.Co > 64 else 64}>", self._flops(c, g),
+        self._timed(conv_tag("wgrad", c.Co), self._flops(c, g),
                     lambda: self._wgrad(x, dz, g, self.G[c.w_off:]), self._bytes(c, g, wgrad=True), layer=c.name)
         if not need_dx:
             return None
@@ -925,7 +992,7 @@ class Engine:
         extra = ((dx_bytes / 4 if addend_half else dx_bytes) if addend is not None else 0.0) + (dx_bytes if bn is not None else 0.0) + \
                 (dx_bytes if relu_mask is not None else 0.0) + (dx_bytes / 16 if (bn is not None and relu_bits is not None) else 0.0) + \
                 (dx_bytes / 16 if (bn is None and relu_mask is None and mask_bits is not None and self.dgrad_mask_bits) else 0.0)
-        self._timed(f"conv_igemm_kernel<{128 if c.Ci > 64 else 64},dgrad>", self._flops(c, g), run, self._bytes(c, g) + extra, layer=c.name)
+        self._timed(conv_tag("igemm", c.Ci, "dgrad"), self._flops(c, g), run, self._bytes(c, g) + extra, layer=c.name)
         return dx
 
     def backward(self, tp: Tape, g_heat: torch.Tensor, trace: dict | None = None) -> None:
@@ -977,26 +1044,26 @@ class Engine:
             # pair (lp_bn_pool_bwd_*).
             dbn_sums = None   # the projection shortcut's BatchNorm reductions, taken by bn3's backward walk over the same gradient where it can
             if last:
-                dz3, dres = self._bn_bwd(blk.bn3, d, T[f"{key}.out"], T[f"{key}.z3"], T[f"{key}.m3"], T[f"{key}.v3"], Mo, True, seg=seg)
+                dz3, dres, _ = self._bn_bwd(blk.bn3, d, T[f"{key}.out"], T[f"{key}.z3"], T[f"{key}.m3"], T[f"{key}.v3"], Mo, True, seg=seg)
             elif blk.down is not None:
                 dz3, _, dbn_sums = self._bn_bwd(blk.bn3, d, None, T[f"{key}.z3"], T[f"{key}.m3"], T[f"{key}.v3"], Mo, False, sums=d_sums, seg=seg,
                                                 ds=(T[f"{key}.zd"], T[f"{key}.md"], T[f"{key}.vd"]))
                 dres = d
             else:
-                dz3, _ = self._bn_bwd(blk.bn3, d, None, T[f"{key}.z3"], T[f"{key}.m3"], T[f"{key}.v3"], Mo, False, sums=d_sums, seg=seg)
+                dz3, _, _ = self._bn_bwd(blk.bn3, d, None, T[f"{key}.z3"], T[f"{key}.m3"], T[f"{key}.v3"], Mo, False, sums=d_sums, seg=seg)
                 dres = d
             s2 = new_sums(blk.bn2)
             da2 = self._conv_bwd(blk.conv3, T[f"{key}.a2"], dz3, B, ho, wo, True,
                                  bn=(blk.bn2, T[f"{key}.z2"], T[f"{key}.m2"], T[f"{key}.v2"], s2), seg=seg)
-            dz2, _ = self._bn_bwd(blk.bn2, da2, None, T[f"{key}.z2"], T[f"{key}.m2"], T[f"{key}.v2"], Mo, False, sums=s2, seg=seg)
+            dz2, _, _ = self._bn_bwd(blk.bn2, da2, None, T[f"{key}.z2"], T[f"{key}.m2"], T[f"{key}.v2"], Mo, False, sums=s2, seg=seg)
             s1 = new_sums(blk.bn1)
             da1 = self._conv_bwd(blk.conv2, T[f"{key}.a1"], dz2, B, hi, wi, True,
                                  bn=(blk.bn1, T[f"{key}.z1"], T[f"{key}.m1"], T[f"{key}.v1"], s1), seg=seg)
-            dz1, _ = self._bn_bwd(blk.bn1, da1, None, T[f"{key}.z1"], T[f"{key}.m1"], T[f"{key}.v1"], Mi, False, sums=s1, seg=seg)
+            dz1, _, _ = self._bn_bwd(blk.bn1, da1, None, T[f"{key}.z1"], T[f"{key}.m1"], T[f"{key}.v1"], Mi, False, sums=s1, seg=seg)
             mask_x = x if i > 0 else None  # block 0's input is the max-pool output: its ReLU is handled by the stem BN backward
             d_sums = None
             if blk.down is not None:
-                dzd, _ = self._bn_bwd(blk.dbn, dres, None, T[f"{key}.zd"], T[f"{key}.md"], T[f"{key}.vd"], Mo, False, sums=dbn_sums, seg=seg)
+                dzd, _, _ = self._bn_bwd(blk.dbn, dres, None, T[f"{key}.zd"], T[f"{key}.md"], T[f"{key}.vd"], Mo, False, sums=dbn_sums, seg=seg)
                 xbits = T.get(f"b{i - 1}.out_bits") if i > 0 else None   # x = the previous block's output: its 1-bit ReLU mask exists
                 if i > 0 and xbits is not None and self.dgrad_half_addend and blk.down.stride == 2 and blk.down.k == 1 and blk.conv1.stride == 1:
                     # The shortcut's data gradient FIRST, on its own (half-resolution) grid - a plain 1x1 product, no read-modify-write of the
@@ -1005,11 +1072,11 @@ class Engine:
                     # stand-alone reduction over the two-writer gradient (lp_bn_bwd_reduce, 2 passes over it) is gone.
                     prev, pk = plan.blocks[i - 1], f"b{i - 1}"
                     gd = self._geom(blk.down, B, hi, wi)
-                    self._timed(f"conv_wgrad_kernel<{128 if blk.down.Co > 64 else 64}>", self._flops(blk.down, gd),
+                    self._timed(conv_tag("wgrad", blk.down.Co), self._flops(blk.down, gd),
                                 lambda: self._wgrad(x, dzd, gd, self.G[blk.down.w_off:]), self._bytes(blk.down, gd, wgrad=True), layer=blk.down.name)
                     gh = _lib.ConvGeom(B, gd.Ho, gd.Wo, blk.down.Ci, gd.Ho, gd.Wo, blk.down.Co, 1, 1, 1, 0)   # the shortcut on its own grid: stride 1
                     dd = torch.empty(B, gd.Ho, gd.Wo, blk.down.Ci, device=self.device, dtype=torch.bfloat16)
-                    self._timed(f"conv_igemm_kernel<{128 if blk.down.Ci > 64 else 64},dgrad>", self._flops(blk.down, gd),
+                    self._timed(conv_tag("igemm", blk.down.Ci, "dgrad"), self._flops(blk.down, gd),
                                 lambda: check(self._lib.lp_conv_dgrad(_p(dzd), _p(self.Wd[blk.down.wd_off:]), C.byref(gh), None, None, None, _p(dd), None,
                                                                       blk.down.Ci, 0, 0, ops._stream()), "lp_conv_dgrad"),
                                 2.0 * B * gd.Ho * gd.Wo * (blk.down.Co + blk.down.Ci), layer=blk.down.name)
@@ -1061,16 +1128,18 @@ class Engine:
                                                  float(n * sh * sw * world), n, sh, sw, 64, _p(dz[i0:i0 + n]), _p(slocal[si * 4 * sb.C:]),
                                                  _p(self.G[sb.b_off:]), _p(self.G[sb.g_off:]), ops._stream()), "lp_bn_pool_bwd_apply")
         g = self._geom(plan.stem, B, H, W)
-        self._timed("conv_wgrad_kernel<64,stem>", self._flops(plan.stem, g),
+        self._timed(conv_tag("wgrad", 64, "stem"), self._flops(plan.stem, g),
                     lambda: self._wgrad(T["x4"], dz, g, self.G[plan.stem.w_off:], stem=True), self._bytes(plan.stem, g, wgrad=True), layer=plan.stem.name)
         self._join_side_stream()
 
 
-class HeadEngine(Engine):
+class HeadEngine(EngineCore):
     """The head alone, for a ``HeatmapHead`` used outside a tracker (reference models/heads/heatmap.py:147-212, as its own tests use it:
     tests/models/heads/test_heatmap.py): PixelShuffle(2) + n ConvTranspose2d + optional spatial soft-max over its own flat buffers, with
     every constructor option of the reference class (``deconv_out_channels``, ``final_softmax``).  Same kernels and tape as the head
     of the full engines; features come and go as (B, C, h, w) fp32, the arithmetic is bf16-mixed like the trunk's."""
+
+    SWITCHES = (("wgrad_side_stream", "LP_WGRAD_SIDE_STREAM", True),)
 
     def __init__(self, in_channels: int, stride: int, num_keypoints: int, downsample_factor: int = 2, deconv_out_channels: int | None = None,
                  final_softmax: bool = True, device: torch.device | str = "cuda:0"):
@@ -1078,29 +1147,14 @@ class HeadEngine(Engine):
             raise NotImplementedError(f"at most {CPAD} heat-map channels are supported, got {num_keypoints}")
         if in_channels % 4:
             raise ValueError(f"PixelShuffle(2) needs a multiple of 4 input channels, got {in_channels}")
-        head = build_head(in_channels, stride, num_keypoints, downsample_factor, deconv_out_channels)
-        plan = Plan(None, None, [], head)
-        off = wd = 0
-        for c in head:
-            c.w_off, c.wd_off = off, wd
-            off += c.numel
-            wd += c.numel
-            c.bias_off = off
-            off += c.Ci
-            plan.convs.append(c)
-        plan.n_backbone, plan.n_total, plan.n_wd, plan.n_running = 0, off, wd, 0
-        super().__init__(num_keypoints, downsample_factor, device, plan=plan)
+        plan = HeadPlan(build_head(in_channels, stride, num_keypoints, downsample_factor, deconv_out_channels))
+        super().__init__(plan, num_keypoints, downsample_factor, device, final_softmax=bool(final_softmax))
         self.in_channels = in_channels
-        self.final_softmax = bool(final_softmax)
 
     def state_dict(self) -> dict[str, torch.Tensor]:
-        sd: dict[str, torch.Tensor] = {}
-        for c in self.plan.head:
-            sd[f"{c.name}.weight"] = self.param_view(c)
-            sd[f"{c.name}.bias"] = self.param_view(c, "bias")
-        return sd
+        return self._head_views()
 
-    def forward(self, features: torch.Tensor, training: bool = True) -> tuple[torch.Tensor, Tape]:   # type: ignore[override]
+    def forward(self, features: torch.Tensor, training: bool = True) -> tuple[torch.Tensor, Tape]:
         ops.require_device(features)
         if features.dim() != 4 or features.shape[1] != self.in_channels:
             raise ValueError(f"features must be (B, {self.in_channels}, h, w), got {tuple(features.shape)}")
@@ -1111,7 +1165,7 @@ class HeadEngine(Engine):
         heat = self._head_forward(x, B, h, w, tp.t)
         return heat, tp
 
-    def backward(self, tp: Tape, g_heat: torch.Tensor, trace: dict | None = None) -> torch.Tensor:   # type: ignore[override]
+    def backward(self, tp: Tape, g_heat: torch.Tensor, trace: dict | None = None) -> torch.Tensor:
         """Parameter gradients accumulate into G; returns d loss / d features (B, C, h, w) fp32."""
         d = self._head_backward(tp.t, tp.meta["B"], g_heat)
         self._join_side_stream()

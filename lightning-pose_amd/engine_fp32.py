@@ -21,107 +21,26 @@ import torch.distributed as dist
 
 from . import ops
 from ._lib import check
-from .engine import BN_EPS, BN_MOMENTUM, BNP, CPAD, ConvP, Engine, Tape
+from .engine import BN_EPS, BN_MOMENTUM, BNP, CPAD, ConvP, Engine, Tape, image_parts
 from .ops import _p
 
 
-class Fp32Engine(Engine):
-    wgrad_side_stream = False
+class Fp32Head:
+    """The head in fp32, over the core's fields: listed first in the bases of both validation executors (Fp32Engine here,
+    vit_engine_fp32.Fp32ViTEngine), where it replaces the core's bf16 ``_head_forward`` / ``_head_backward``."""
+
     precision = "fp32"
 
-    # ------------------------------------------------------------------------------------------------ kernels
     @staticmethod
     def _wdims(c: ConvP) -> tuple[int, int, int]:
         """storage dims (KH, KW, CiS) of the layer's weight in the flat buffer"""
         return (8, 8, 4) if c.kind == "stem" else (c.k, c.k, c.Ci)
 
-    def can_segment(self, n0: int, H: int, W: int) -> bool:
-        """nothing is fused into tiles here: two BatchNorm segments are simply two calls of the BatchNorm kernels"""
-        return n0 > 0
-
     def _f32(self, *shape) -> torch.Tensor:
         return torch.empty(*shape, device=self.device, dtype=torch.float32)
 
-    def _conv(self, c: ConvP, x: torch.Tensor, B: int, Hi: int, Wi: int):
-        g = self._geom(c, B, Hi, Wi)
-        out = self._f32(B, g.Ho, g.Wo, c.Co)
-        check(self._lib.lp_f32_conv_fwd(_p(x), _p(self.P[c.w_off:]), C.byref(g), *self._wdims(c), None, None, _p(out), ops._stream()),
-              "lp_f32_conv_fwd")
-        return out, g
-
-    def _dgrad(self, c: ConvP, dy: torch.Tensor, g, addend: torch.Tensor | None = None) -> torch.Tensor:
-        dx = self._f32(g.B, g.Hi, g.Wi, g.Ci)
-        check(self._lib.lp_f32_conv_dgrad(_p(dy), _p(self.P[c.w_off:]), C.byref(g), *self._wdims(c), None, _p(addend), _p(dx), ops._stream()),
-              "lp_f32_conv_dgrad")
-        return dx
-
     def _wg(self, c: ConvP, x: torch.Tensor, dy: torch.Tensor, g) -> None:
         check(self._lib.lp_f32_conv_wgrad(_p(x), _p(dy), C.byref(g), *self._wdims(c), _p(self.G[c.w_off:]), ops._stream()), "lp_f32_conv_wgrad")
-
-    def _bn(self, b: BNP, z: torch.Tensor, residual, relu: bool, training: bool, seg: int):
-        """-> (y, mean, invstd); mean / invstd are (segments, C) flattened"""
-        B = z.shape[0]
-        M = z.numel() // b.C
-        rpi = M // B
-        segs = self._segments(B, seg if training else 0)
-        mean = self._f32(len(segs) * b.C)
-        invstd = torch.empty_like(mean)
-        if training:
-            sums = torch.zeros(len(segs) * 2 * b.C, device=self.device, dtype=torch.float32)
-            for si, (i0, n) in enumerate(segs):   # ordered partial sums (no atomics): the validation forward repeats bit for bit
-                need = int(self._lib.lp_f32_bn_stats_workspace_bytes(n * rpi, b.C))
-                if getattr(self, "_stats_ws", None) is None or self._stats_ws.numel() < need:
-                    self._stats_ws = torch.empty(need, device=self.device, dtype=torch.uint8)
-                check(self._lib.lp_f32_bn_stats_ordered(_p(z[i0:i0 + n]), n * rpi, b.C, _p(sums[si * 2 * b.C:]), _p(self._stats_ws),
-                                                        self._stats_ws.numel(), ops._stream()), "lp_f32_bn_stats_ordered")
-            counts = [float(n * rpi) for _, n in segs]
-            if self.sync_bn:
-                self._sync_stats(sums)
-                self.sync_bn_messages += 1
-                counts = [c_ * dist.get_world_size(self.process_group) for c_ in counts]
-            rm, rv = _p(self.running_view(b, "running_mean")), _p(self.running_view(b, "running_var"))
-            for si in range(len(segs)):   # segment 0's running-statistics update, then segment 1's (the reference's two forward calls)
-                check(self._lib.lp_bn_finalize_f32(_p(sums[si * 2 * b.C:]), counts[si], b.C, BN_EPS, BN_MOMENTUM, _p(mean[si * b.C:]),
-                                                   _p(invstd[si * b.C:]), rm, rv, ops._stream()), "lp_bn_finalize_f32")
-        else:
-            mean.copy_(self.running_view(b, "running_mean"))
-            invstd.copy_((self.running_view(b, "running_var") + BN_EPS).rsqrt())
-        y = torch.empty_like(z)
-        gam, bet = _p(self.param_view(b, "weight")), _p(self.param_view(b, "bias"))
-        for si, (i0, n) in enumerate(segs):
-            check(self._lib.lp_f32_bn_apply(_p(z[i0:i0 + n]), _p(mean[si * b.C:]), _p(invstd[si * b.C:]), gam, bet,
-                                            _p(residual[i0:i0 + n]) if residual is not None else None, int(relu), n * rpi, b.C,
-                                            _p(y[i0:i0 + n]), ops._stream()), "lp_f32_bn_apply")
-        return y, mean, invstd
-
-    def _bn_back(self, b: BNP, dy, y_out, z, mean, invstd, want_dres: bool, seg: int):
-        """gradient of relu?(BN(z) [+ residual]) w.r.t. z (and, with want_dres, the ReLU-masked gradient for the residual branch)"""
-        B = z.shape[0]
-        M = z.numel() // b.C
-        rpi = M // B
-        segs = self._segments(B, seg)
-        Cn = b.C
-        sums = torch.zeros(len(segs) * 2 * Cn, device=self.device, dtype=torch.float32)
-        for si, (i0, n) in enumerate(segs):
-            check(self._lib.lp_f32_bn_bwd_reduce(_p(dy[i0:i0 + n]), _p(y_out[i0:i0 + n]) if y_out is not None else None, _p(z[i0:i0 + n]),
-                                                 _p(mean[si * Cn:]), _p(invstd[si * Cn:]), n * rpi, Cn, _p(sums[si * 2 * Cn:]),
-                                                 _p(self.G[b.b_off:]), _p(self.G[b.g_off:]), ops._stream()), "lp_f32_bn_bwd_reduce")
-        world = 1
-        if not self._bwd_training:
-            sums = torch.zeros_like(sums)  # eval-mode BatchNorm: a fixed affine map, no batch-statistics terms
-        elif self.sync_bn:
-            self._sync_stats(sums)
-            self.sync_bn_messages += 1
-            world = dist.get_world_size(self.process_group)
-        dz = torch.empty_like(z)
-        dres = torch.empty_like(z) if want_dres else None
-        gam = _p(self.param_view(b, "weight"))
-        for si, (i0, n) in enumerate(segs):
-            check(self._lib.lp_f32_bn_bwd_apply(_p(dy[i0:i0 + n]), _p(y_out[i0:i0 + n]) if y_out is not None else None, _p(z[i0:i0 + n]),
-                                                _p(mean[si * Cn:]), _p(invstd[si * Cn:]), gam, _p(sums[si * 2 * Cn:]), float(n * rpi * world),
-                                                n * rpi, Cn, _p(dz[i0:i0 + n]), _p(dres[i0:i0 + n]) if want_dres else None, ops._stream()),
-                  "lp_f32_bn_bwd_apply")
-        return dz, dres
 
     # ------------------------------------------------------------------------------------------------ head
     def _head_forward(self, x: torch.Tensor, B: int, h: int, w: int, T: dict) -> torch.Tensor:
@@ -175,20 +94,100 @@ class Fp32Engine(Engine):
         check(self._lib.lp_f32_pixel_shuffle(_p(dcur), B, fh, fw, cs, ld, 1, _p(d), ops._stream()), "lp_f32_pixel_shuffle(inv)")
         return d
 
+
+class Fp32Engine(Fp32Head, Engine):
+    """The ResNet-50 trunk of ``Engine`` with every activation and contraction in fp32 (module docstring)."""
+
+    def __init__(self, num_keypoints: int, downsample_factor: int = 2, device: torch.device | str = "cuda:0"):
+        super().__init__(num_keypoints, downsample_factor, device)
+        self._stats_ws: torch.Tensor | None = None   # partial sums of lp_f32_bn_stats_ordered
+
+    # ------------------------------------------------------------------------------------------------ kernels
+    def can_segment(self, n0: int, H: int, W: int) -> bool:
+        """nothing is fused into tiles here: two BatchNorm segments are simply two calls of the BatchNorm kernels"""
+        return n0 > 0
+
+    def _conv(self, c: ConvP, x: torch.Tensor, B: int, Hi: int, Wi: int):
+        g = self._geom(c, B, Hi, Wi)
+        out = self._f32(B, g.Ho, g.Wo, c.Co)
+        check(self._lib.lp_f32_conv_fwd(_p(x), _p(self.P[c.w_off:]), C.byref(g), *self._wdims(c), None, None, _p(out), ops._stream()),
+              "lp_f32_conv_fwd")
+        return out, g
+
+    def _dgrad(self, c: ConvP, dy: torch.Tensor, g, addend: torch.Tensor | None = None) -> torch.Tensor:
+        dx = self._f32(g.B, g.Hi, g.Wi, g.Ci)
+        check(self._lib.lp_f32_conv_dgrad(_p(dy), _p(self.P[c.w_off:]), C.byref(g), *self._wdims(c), None, _p(addend), _p(dx), ops._stream()),
+              "lp_f32_conv_dgrad")
+        return dx
+
+    def _bn(self, b: BNP, z: torch.Tensor, residual, relu: bool, training: bool, seg: int):
+        """-> (y, mean, invstd); mean / invstd are (segments, C) flattened"""
+        B = z.shape[0]
+        M = z.numel() // b.C
+        rpi = M // B
+        segs = self._segments(B, seg if training else 0)
+        mean = self._f32(len(segs) * b.C)
+        invstd = torch.empty_like(mean)
+        if training:
+            sums = torch.zeros(len(segs) * 2 * b.C, device=self.device, dtype=torch.float32)
+            for si, (i0, n) in enumerate(segs):   # ordered partial sums (no atomics): the validation forward repeats bit for bit
+                need = int(self._lib.lp_f32_bn_stats_workspace_bytes(n * rpi, b.C))
+                if self._stats_ws is None or self._stats_ws.numel() < need:
+                    self._stats_ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+                check(self._lib.lp_f32_bn_stats_ordered(_p(z[i0:i0 + n]), n * rpi, b.C, _p(sums[si * 2 * b.C:]), _p(self._stats_ws),
+                                                        self._stats_ws.numel(), ops._stream()), "lp_f32_bn_stats_ordered")
+            counts = [float(n * rpi) for _, n in segs]
+            if self.sync_bn:
+                self._sync_stats(sums)
+                self.sync_bn_messages += 1
+                counts = [c_ * dist.get_world_size(self.process_group) for c_ in counts]
+            rm, rv = _p(self.running_view(b, "running_mean")), _p(self.running_view(b, "running_var"))
+            for si in range(len(segs)):   # segment 0's running-statistics update, then segment 1's (the reference's two forward calls)
+                check(self._lib.lp_bn_finalize_f32(_p(sums[si * 2 * b.C:]), counts[si], b.C, BN_EPS, BN_MOMENTUM, _p(mean[si * b.C:]),
+                                                   _p(invstd[si * b.C:]), rm, rv, ops._stream()), "lp_bn_finalize_f32")
+        else:
+            mean.copy_(self.running_view(b, "running_mean"))
+            invstd.copy_((self.running_view(b, "running_var") + BN_EPS).rsqrt())
+        y = torch.empty_like(z)
+        gam, bet = _p(self.param_view(b, "weight")), _p(self.param_view(b, "bias"))
+        for si, (i0, n) in enumerate(segs):
+            check(self._lib.lp_f32_bn_apply(_p(z[i0:i0 + n]), _p(mean[si * b.C:]), _p(invstd[si * b.C:]), gam, bet,
+                                            _p(residual[i0:i0 + n]) if residual is not None else None, int(relu), n * rpi, b.C,
+                                            _p(y[i0:i0 + n]), ops._stream()), "lp_f32_bn_apply")
+        return y, mean, invstd
+
+    def _bn_back(self, b: BNP, dy, y_out, z, mean, invstd, want_dres: bool, seg: int):
+        """gradient of relu?(BN(z) [+ residual]) w.r.t. z (and, with want_dres, the ReLU-masked gradient for the residual branch)"""
+        B = z.shape[0]
+        M = z.numel() // b.C
+        rpi = M // B
+        segs = self._segments(B, seg)
+        Cn = b.C
+        sums = torch.zeros(len(segs) * 2 * Cn, device=self.device, dtype=torch.float32)
+        for si, (i0, n) in enumerate(segs):
+            check(self._lib.lp_f32_bn_bwd_reduce(_p(dy[i0:i0 + n]), _p(y_out[i0:i0 + n]) if y_out is not None else None, _p(z[i0:i0 + n]),
+                                                 _p(mean[si * Cn:]), _p(invstd[si * Cn:]), n * rpi, Cn, _p(sums[si * 2 * Cn:]),
+                                                 _p(self.G[b.b_off:]), _p(self.G[b.g_off:]), ops._stream()), "lp_f32_bn_bwd_reduce")
+        world = 1
+        if not self._bwd_training:
+            sums = torch.zeros_like(sums)  # eval-mode BatchNorm: a fixed affine map, no batch-statistics terms
+        elif self.sync_bn:
+            self._sync_stats(sums)
+            self.sync_bn_messages += 1
+            world = dist.get_world_size(self.process_group)
+        dz = torch.empty_like(z)
+        dres = torch.empty_like(z) if want_dres else None
+        gam = _p(self.param_view(b, "weight"))
+        for si, (i0, n) in enumerate(segs):
+            check(self._lib.lp_f32_bn_bwd_apply(_p(dy[i0:i0 + n]), _p(y_out[i0:i0 + n]) if y_out is not None else None, _p(z[i0:i0 + n]),
+                                                _p(mean[si * Cn:]), _p(invstd[si * Cn:]), gam, _p(sums[si * 2 * Cn:]), float(n * rpi * world),
+                                                n * rpi, Cn, _p(dz[i0:i0 + n]), _p(dres[i0:i0 + n]) if want_dres else None, ops._stream()),
+                  "lp_f32_bn_bwd_apply")
+        return dz, dres
+
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, images, training: bool = True) -> tuple[torch.Tensor, Tape]:
-        parts = list(images) if isinstance(images, (list, tuple)) else [images]
-        for p_ in parts:
-            ops.require_device(p_)
-        parts = [p_.to(torch.float32).contiguous() for p_ in parts]
-        if parts[0].dim() != 4 or parts[0].shape[1] != 3:
-            raise ValueError(f"images must be (B, 3, H, W), got {tuple(parts[0].shape)}")   # (raw pointers from here on)
-        _, _, H, W = parts[0].shape
-        if H % 32 or W % 32:
-            raise ValueError(f"image size must be a multiple of 32, got {H}x{W}")
-        if len(parts) > 2 or any(p_.shape[1:] != parts[0].shape[1:] for p_ in parts):
-            raise ValueError("a joint pass takes at most two batches of equally sized images")
-        B = sum(p_.shape[0] for p_ in parts)
+        parts, B, H, W = image_parts(images, 32, 2)
         seg = parts[0].shape[0] if (len(parts) == 2 and training) else 0
         tp = Tape()
         T, plan = tp.t, self.plan

@@ -20,7 +20,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -28,7 +27,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .engine import ConvP, Engine, Tape, build_head
+from .engine import ConvP, EngineCore, Tape, build_head, image_parts, place_head
 from .ops import _p
 
 LN_EPS = 1e-12  # ViTConfig.layer_norm_eps
@@ -127,17 +126,8 @@ class ViTPlan:
         self.lnf = ln(f"{pre}.layernorm")
         self.n_backbone = off
         self.head: list[ConvP] = build_head(D, patch, num_keypoints, downsample_factor)
-        self.convs: list[ConvP] = []
-        self.bns: list = []
-        for c in self.head:
-            c.w_off = off
-            off += c.numel
-            c.wd_off = wd
-            wd += c.numel
-            c.bias_off = off
-            off += c.Ci
-            self.convs.append(c)
-        self.n_total, self.n_wd = off, wd
+        self.convs: list[ConvP] = list(self.head)
+        self.n_total, self.n_wd = place_head(self.head, off, wd)
         self.n_running = 0
 
     def group_ranges(self) -> dict[str, tuple[int, int]]:
@@ -160,7 +150,7 @@ class ViTPlan:
         return out + [self.lnf]
 
 
-class ViTEngine(Engine):
+class ViTEngine(EngineCore):
     """ViT-S/16 defaults = facebook/dino-vits16 (hidden 384, 12 layers, 6 heads, MLP 1536, patch 16, 224-px position table).
 
     ``num_views`` = V > 0 selects the multi-view mode (reference models/heatmap_tracker_multiview.py:143-223, ``forward_vit``): the batch is
@@ -175,52 +165,37 @@ class ViTEngine(Engine):
     ``lp_layernorm_ls_bwd`` emits the scaled gradient, its column sums and the scale's own gradient; the tape keeps the two
     unscaled branch outputs of every layer for the latter.  Single-view only."""
 
-    wgrad_side_stream = False
+    # A/B switches (EngineCore.SWITCHES).  bias_fused: every LayerNorm / GELU backward leaves the column sums that are the next Linear
+    # layer's bias gradient (0: the weight-gradient launches take them).  gelu_fused: GELU inside fc1's store pass and fc2's data gradient
+    # (round 6); "bwd": only the latter; "0": neither - lp_gelu_fwd / lp_gemm_nt, then lp_gelu_bwd_colsum
+    SWITCHES = (("bias_fused", "LP_VIT_BIAS_FUSED", True), ("gelu_fused", "LP_VIT_GELU_FUSED", "1"))
     _patch_dtype = torch.bfloat16
     _token_kernels = ("lp_vit_tokens_fwd", "lp_vit_tokens_bwd", "lp_vit_mv_tokens_fwd", "lp_vit_mv_tokens_bwd")
 
     def __init__(self, num_keypoints: int, downsample_factor: int = 2, device: torch.device | str = "cuda:0", hidden: int = 384,
                  depth: int = 12, heads: int = 6, mlp: int = 1536, patch: int = 16, pretrain_grid: int = 14, num_views: int = 0,
                  arch: str = "vit"):
-        self.device = torch.device(device)
-        ops.require_device_type(self.device)
-        self._lib = _lib.lib()
-        self.K, self.ds = num_keypoints, downsample_factor
         if hidden % 64 or (hidden // heads) != 64 or mlp % 64:
             raise NotImplementedError("ViT widths must be multiples of 64 with 64-wide heads (ViT-S/B)")
-        self.grid0 = pretrain_grid
         if num_views < 0:
             raise ValueError(f"num_views must be positive (0: single-view tokens with [CLS]), got {num_views}")
         if arch not in ("vit", "dinov2"):
             raise ValueError(f'arch must be "vit" or "dinov2", got {arch!r}')
         if arch == "dinov2" and num_views:
             raise NotImplementedError("the multi-view token assembly (num_views > 0) is not implemented for the DINOv2 backbones")
+        super().__init__(ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, 1 + pretrain_grid * pretrain_grid,
+                                 num_views, arch), num_keypoints, downsample_factor, device)
+        self.grid0 = pretrain_grid
         self.arch = arch
         self.ln_eps = DINOV2_LN_EPS if arch == "dinov2" else LN_EPS
-        self.plan = ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, 1 + pretrain_grid * pretrain_grid, num_views,
-                            arch)
-        n, dev = self.plan.n_total, self.device
-        self.P = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.G = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.Wb = torch.zeros(n, device=dev, dtype=torch.bfloat16)
-        self.Wd = torch.zeros(self.plan.n_wd, device=dev, dtype=torch.bfloat16)
-        self.R = torch.zeros(0, device=dev, dtype=torch.float32)
         for l in self.plan.norms():
             self.P[l.g_off:l.g_off + hidden] = 1.0
         for L in self.plan.layers:   # (Dinov2Config.layerscale_value = 1.0)
             for o in (L.get("ls1"), L.get("ls2")):
                 if o is not None:
                     self.P[o:o + hidden] = 1.0
-        self.nbt = torch.zeros((), dtype=torch.long)
-        self.sync_bn, self.process_group = False, None   # no BatchNorm here; kept for the DataParallel wrapper
-        self.sync_bn_messages = 0
-        self.grad_progress, self.single_backward = None, False   # gradient buckets leave during backward (Engine.backward, distributed.py)
-        self._bwd_training = True
-        self.profile = None
-        self._wgrad_ws = None
-        self._side, self._side_busy, self._side_keep = None, False, []
-        self._fold = None
-        self._interp: dict[tuple[int, int], torch.Tensor] = {}
+        self._interp: dict[tuple[int, int], torch.Tensor] = {}   # bicubic resize matrices of the position table, by patch grid
+        self._wg_shape = (0, 0)   # (sequences, tokens) of the pass in flight: the image geometry _linear_bwd gives the weight-gradient kernel
 
     # ------------------------------------------------------------------------------------------------ params
     def _views(self, buf: torch.Tensor) -> dict[str, torch.Tensor]:
@@ -251,9 +226,7 @@ class ViTEngine(Engine):
             for i, L in enumerate(pl.layers):
                 for nm in ("1", "2"):
                     sd[f"{pre}.encoder.layer.{i}.layer_scale{nm}.lambda1"] = buf[L["ls" + nm]:L["ls" + nm] + D]
-        for c in pl.head:
-            sd[f"{c.name}.weight"] = self.param_view(c, "weight", buf=buf)
-            sd[f"{c.name}.bias"] = self.param_view(c, "bias", buf=buf)
+        sd.update(self._head_views(buf))
         return sd
 
     def state_dict(self) -> dict[str, torch.Tensor]:
@@ -278,25 +251,14 @@ class ViTEngine(Engine):
     def load_state_dict(self, sd: dict[str, torch.Tensor], strict: bool = True) -> None:
         if self.arch != "dinov2":   # (Dinov2Model's own names are the 4.x-style ones: nothing to translate)
             sd = {self.canonical_key(k): v for k, v in sd.items()}
-        own = self.state_dict()
-        missing = [k for k in own if k not in sd]
-        unexpected = [k for k in sd if k not in own]
-        if strict and (missing or unexpected):
-            raise KeyError(f"state_dict mismatch: missing {missing[:5]}..., unexpected {unexpected[:5]}...")
-        for k, dst in own.items():
-            if k in sd:
-                dst.copy_(sd[k].to(device=self.device, dtype=torch.float32).reshape(dst.shape))
-        self.refresh_weight_copies()
+        EngineCore.load_state_dict(self, sd, strict)
 
     def refresh_dgrad_copies(self, lo: int = 0, hi: int | None = None) -> None:
         hi = self.plan.n_total if hi is None else hi
         for l in self.plan.linears():
             if lo <= l.w_off < hi:  # [N][K] -> [K][N]
                 check(self._lib.lp_permute_cba(_p(self.Wb[l.w_off:]), l.N, 1, l.K, _p(self.Wd[l.wd_off:]), ops._stream()), "lp_permute_cba")
-        for c in self.plan.convs:
-            if lo <= c.w_off < hi:
-                check(self._lib.lp_permute_cba(_p(self.Wb[c.w_off:]), c.Co, c.k * c.k, c.Ci, _p(self.Wd[c.wd_off:]), ops._stream()),
-                      "lp_permute_cba")
+        EngineCore.refresh_dgrad_copies(self, lo, hi)   # (the head's convolutions)
 
     # ------------------------------------------------------------------------------------------------ kernels
     def _gemm(self, a, lda, b, ldb, M, N, K, out, ldc, n_store=0, bias=None, batch=None):
@@ -321,7 +283,7 @@ class ViTEngine(Engine):
         shape the pipelined kernel does not tile: the Linear layer, then lp_gelu_fwd"""
         u = torch.empty(M, l.N, device=self.device, dtype=torch.bfloat16)
         act = torch.empty_like(u)
-        if os.environ.get("LP_VIT_GELU_FUSED", "1") not in ("0", "bwd"):
+        if self.gelu_fused not in ("0", "bwd"):
             rc = self._timed("lp_gemm_nt<linear fwd+gelu>", 2.0 * M * l.N * l.K, lambda: self._lib.lp_gemm_nt_gelu_fwd(
                 _p(x), _p(self.Wb[l.w_off:]), _p(self.P[l.b_off:l.b_off + l.N]), _p(u), _p(act), M, l.N, l.K, ops._stream()),
                 nbytes=2.0 * (M * l.K + 2 * M * l.N + l.N * l.K))
@@ -491,20 +453,9 @@ class ViTEngine(Engine):
         return self._forward(images, False, keep=False)[0]
 
     def _forward(self, images, training: bool, keep: bool) -> tuple[torch.Tensor, Tape]:
-        parts = list(images) if isinstance(images, (list, tuple)) else [images]
-        for p_ in parts:
-            ops.require_device(p_)
-        parts = [p_.to(torch.float32).contiguous() for p_ in parts]
-        if any(p_.shape[1:] != parts[0].shape[1:] for p_ in parts):
-            raise ValueError("a joint pass takes batches of equally sized images")
-        if parts[0].dim() != 4 or parts[0].shape[1] != 3:
-            raise ValueError(f"images must be (B, 3, H, W), got {tuple(parts[0].shape)}")   # (raw pointers from here on)
-        _, _, H, W = parts[0].shape
-        B = sum(p_.shape[0] for p_ in parts)
         pl = self.plan
         D, nh, pt = pl.D, pl.heads, pl.patch
-        if H % pt or W % pt:
-            raise ValueError(f"image size must be a multiple of the patch size {pt}, got {H}x{W}")
+        parts, B, H, W = image_parts(images, pt, None, of="the patch size ")
         gh, gw = H // pt, W // pt
         Np = gh * gw
         Bs, Tn, drop_T = self._seq(parts, Np)   # (B images; the layers see Bs sequences of Tn tokens)
@@ -577,8 +528,8 @@ class ViTEngine(Engine):
         dx = torch.zeros(M, D, device=dev, dtype=torch.float32)         # gradient of the residual stream
         # every LayerNorm backward also leaves the updated stream gradient in bf16: it is the operand of the next Linear backward
         # ... and its column sums are the bias gradient of that layer (fc2 of the last block here), so no weight gradient needs a bias pass
-        fuse_bias = os.environ.get("LP_VIT_BIAS_FUSED", "1") != "0"
-        fuse_gelu = os.environ.get("LP_VIT_GELU_FUSED", "1") != "0"   # (0: A/B runs - lp_gemm_nt, then lp_gelu_bwd_colsum)
+        fuse_bias = self.bias_fused
+        fuse_gelu = self.gelu_fused != "0"   # (0: A/B runs - lp_gemm_nt, then lp_gelu_bwd_colsum)
         bsum = (lambda lin: self.G[lin.b_off:lin.b_off + lin.N]) if fuse_bias else (lambda lin: None)
         # (DINOv2: each of them also applies the LayerScale of the branch its bf16 output feeds, and leaves that scale's gradient)
         def scaled(j: int, nm: str) -> dict:

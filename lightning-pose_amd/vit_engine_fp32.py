@@ -14,26 +14,20 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .engine import Tape
-from .engine_fp32 import Fp32Engine
+from .engine import Tape, image_parts
+from .engine_fp32 import Fp32Head
 from .ops import _p
 from .vit_engine import Lin, LNP, ViTEngine
 
 
-class Fp32ViTEngine(ViTEngine):
+class Fp32ViTEngine(Fp32Head, ViTEngine):
     """config C4 (ViT-S/16, reference models/backbones/vit.py:16-49 over HuggingFace ``ViTModel``) in the reference's own precision:
     the plan, flat buffers, state_dict names and optimiser of :class:`ViTEngine`, every tensor and contraction fp32
     (csrc/vit_f32.hip for LayerNorm / GELU / tokens / attention, lp_f32_conv_* with a 1x1 geometry for the Linear layers, the head of
-    :class:`Fp32Engine`).  VALIDATION path: untuned, selected with ``precision="fp32"`` / ``LP_PRECISION=fp32``."""
+    :class:`Fp32Engine`: ``Fp32Head``).  VALIDATION path: untuned, selected with ``precision="fp32"`` / ``LP_PRECISION=fp32``."""
 
-    precision = "fp32"
     _patch_dtype = torch.float32
     _token_kernels = ("lp_f32_vit_tokens_fwd", "lp_f32_vit_tokens_bwd", "lp_f32_vit_mv_tokens_fwd", "lp_f32_vit_mv_tokens_bwd")
-    _f32 = Fp32Engine._f32
-    _wdims = staticmethod(Fp32Engine._wdims)
-    _wg = Fp32Engine._wg
-    _head_forward = Fp32Engine._head_forward
-    _head_backward = Fp32Engine._head_backward
 
     @staticmethod
     def _lin_geom(l: Lin, M: int):
@@ -84,20 +78,9 @@ class Fp32ViTEngine(ViTEngine):
         return dx.clone() if want_bf16 else None   # (the operand of the next Linear backward: dx itself moves on in place)
 
     def _forward(self, images, training: bool, keep: bool):
-        parts = list(images) if isinstance(images, (list, tuple)) else [images]
-        for p_ in parts:
-            ops.require_device(p_)
-        parts = [p_.to(torch.float32).contiguous() for p_ in parts]
-        if any(p_.shape[1:] != parts[0].shape[1:] for p_ in parts):
-            raise ValueError("a joint pass takes batches of equally sized images")
-        if parts[0].dim() != 4 or parts[0].shape[1] != 3:
-            raise ValueError(f"images must be (B, 3, H, W), got {tuple(parts[0].shape)}")
-        _, _, H, W = parts[0].shape
-        B = sum(p_.shape[0] for p_ in parts)
         pl = self.plan
         D, nh, pt = pl.D, pl.heads, pl.patch
-        if H % pt or W % pt:
-            raise ValueError(f"image size must be a multiple of the patch size {pt}, got {H}x{W}")
+        parts, B, H, W = image_parts(images, pt, None, of="the patch size ")
         gh, gw = H // pt, W // pt
         Np = gh * gw
         Bs, Tn, drop_T = self._seq(parts, Np)   # (B images; the layers see Bs sequences of Tn tokens)
