@@ -52,8 +52,9 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * e.g., the stream argument for an inserted flag without any error.  History: 131 = round 5 (decode `prune`, bn_bwd `terms_ws`), 140 = round 6,
  * 144 = the multi-view token assembly (lp_vit_mv_tokens_*), 145 = the camera geometry of the calibrated 3-D losses (lp_cam_*),
  * 146 = patch masking (lp_patch_mask_f32), 147 = LayerScale inside the LayerNorm walks (lp_layernorm_ls_*, the DINOv2 backbones),
- * 148 = the multi-view labeled batch with its 3-D augmentation (lp_mv3d_*), 149 = lp_conv_last_resident. */
-#define LP_HIP_ABI_VERSION 149
+ * 148 = the multi-view labeled batch with its 3-D augmentation (lp_mv3d_*), 149 = lp_conv_last_resident,
+ * 150 = the DINOv3 backbones: lp_rope_*, lp_vit_reg_tokens_*, the prefix-dropping lp_layernorm_ls_*_px (and their fp32 forms). */
+#define LP_HIP_ABI_VERSION 150
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -415,6 +416,18 @@ int lp_f32_layernorm_ls_fwd(const float* x, const float* delta, const float* ls,
 int lp_f32_layernorm_ls_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
                             const float* branch, int M, int D, int drop_T, float* dx_acc, float* dx_out, float* dgamma_acc, float* dbeta_acc,
                             float* colsum_acc, float* dls_acc, lp_stream_t stream);
+/* the fp32 forms of lp_layernorm_ls_fwd_px / _bwd_px, lp_rope_fwd / _bwd and lp_vit_reg_tokens_fwd / _bwd (below): float rows, the same table */
+int lp_f32_layernorm_ls_fwd_px(const float* x, const float* delta, const float* ls, float* x_out, const float* gamma, const float* beta,
+                               float eps, int M, int D, int drop_T, int n_prefix, float* y, float* mean, float* rstd, lp_stream_t stream);
+int lp_f32_layernorm_ls_bwd_px(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
+                               const float* branch, int M, int D, int drop_T, int n_prefix, float* dx_acc, float* dx_out, float* dgamma_acc,
+                               float* dbeta_acc, float* colsum_acc, float* dls_acc, lp_stream_t stream);
+int lp_f32_rope_fwd(float* qkv, int ld, int k_off, const float* table, const int* tab_of_seq, int n_tab, int B, int T, int n_prefix, int nh,
+                    int head_dim, lp_stream_t stream);
+int lp_f32_rope_bwd(float* dqkv, int ld, int k_off, const float* table, const int* tab_of_seq, int n_tab, int B, int T, int n_prefix, int nh,
+                    int head_dim, lp_stream_t stream);
+int lp_f32_vit_reg_tokens_fwd(const float* patch, const float* cls, const float* reg, int B, int R, int Np, int D, float* x, lp_stream_t stream);
+int lp_f32_vit_reg_tokens_bwd(const float* dx, int B, int R, int Np, int D, float* dpatch, float* dcls, float* dreg, lp_stream_t stream);
 int lp_f32_gelu_fwd(const float* x, size_t n, float* y, lp_stream_t stream);
 int lp_f32_gelu_bwd(const float* x, const float* dy, size_t n, float* dx, lp_stream_t stream);
 int lp_f32_attn_fwd(const float* qkv, int ld, int k_off, int v_off, int B, int nh, int T, float scale, float* p, float* o, int ldo,
@@ -608,6 +621,38 @@ int lp_layernorm_ls_fwd(const float* x, const void* delta_bf16, const float* ls,
 int lp_layernorm_ls_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
                         const void* branch_bf16, int M, int D, int drop_T, float* dx_acc, void* dx_bf16, float* dgamma_acc, float* dbeta_acc,
                         float* colsum_acc, float* dls_acc, lp_stream_t stream);
+/* The DINOv3 backbones ("vits_dinov3" / "vitb_dinov3", transformers DINOv3ViTModel): csrc/rope.hip and two more forms of the walks above.
+ *
+ * lp_layernorm_ls_fwd_px / _bwd_px: lp_layernorm_ls_fwd / _bwd with the `n_prefix` leading rows of every drop_T rows ([CLS] and the register
+ *   tokens) dropped from y / carrying no dy, instead of row 0 alone: y holds the (M / drop_T) * (drop_T - n_prefix) kept rows in order
+ *   (0 <= n_prefix <= drop_T; drop_T = 0: nothing dropped).  The same kernels: n_prefix = 1 gives the bits of the forms above.  Dropped rows
+ *   still carry stream gradient and contribute to dgamma / dbeta (with a zero dy) / colsum / dls.
+ *
+ * lp_rope_fwd / _bwd: the rotary position embedding on the Q and K columns of the fused token rows qkv[(b * T + t) * ld + ...] (Q of head h at
+ *   column h * 64, K at k_off + h * 64), IN PLACE, for the rows t >= n_prefix of each of the B sequences of T tokens; the prefix rows, the V
+ *   columns and everything else in the row are neither read nor written.  `table` is (n_tab, T - n_prefix, 64) fp32: per patch token
+ *   cos[0:32] | sin[0:32] (the 32 distinct columns of the head's 64); sequence b uses table tab_of_seq[b] (a device int32 array; NULL: table 0
+ *   for all; an index outside [0, n_tab) is clamped), so a joint pass of two batches with their own coordinate draws is one launch.
+ *   forward, for d < 32: out[d] = x[d] cos[d] - x[d + 32] sin[d],  out[d + 32] = x[d + 32] cos[d] + x[d] sin[d] - in fp32, two products and
+ *   one sum / difference (never a fused multiply-add), one rounding to bf16 (nearest even).  backward: the transposed rotation (sin -> -sin)
+ *   of dQ / dK.  No LDS, no atomics: two runs give the same bits.  LP_ERR_UNSUPPORTED: head_dim != 64, or ld / k_off / a base pointer that
+ *   breaks 16-byte alignment; LP_ERR_ARGUMENT: null qkv / table, non-positive sizes, n_prefix outside [0, T], Q / K blocks outside the row.
+ *
+ * lp_vit_reg_tokens_fwd / _bwd: the token assembly with R >= 0 register tokens and no position table (D % 8 == 0):
+ *   x[b][0] = cls,  x[b][1 + r] = reg[r],  x[b][1 + R + p] = float(patch[b * Np + p]);  backward: dpatch = bf16(dx[:, 1 + R:]),
+ *   dcls = sum_b dx[b][0], dreg[r] = sum_b dx[b][1 + r] - images in ascending order, no atomics, WRITTEN (not accumulated), as
+ *   lp_vit_mv_tokens_bwd does.  reg / dreg may be NULL when R = 0. */
+int lp_layernorm_ls_fwd_px(const float* x, const void* delta_bf16, const float* ls, float* x_out, const float* gamma, const float* beta,
+                           float eps, int M, int D, int drop_T, int n_prefix, void* y_bf16, float* mean, float* rstd, lp_stream_t stream);
+int lp_layernorm_ls_bwd_px(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
+                           const void* branch_bf16, int M, int D, int drop_T, int n_prefix, float* dx_acc, void* dx_bf16, float* dgamma_acc,
+                           float* dbeta_acc, float* colsum_acc, float* dls_acc, lp_stream_t stream);
+int lp_rope_fwd(void* qkv_bf16, int ld, int k_off, const float* table, const int* tab_of_seq, int n_tab, int B, int T, int n_prefix, int nh,
+                int head_dim, lp_stream_t stream);
+int lp_rope_bwd(void* dqkv_bf16, int ld, int k_off, const float* table, const int* tab_of_seq, int n_tab, int B, int T, int n_prefix, int nh,
+                int head_dim, lp_stream_t stream);
+int lp_vit_reg_tokens_fwd(const void* patch_bf16, const float* cls, const float* reg, int B, int R, int Np, int D, float* x, lp_stream_t stream);
+int lp_vit_reg_tokens_bwd(const float* dx, int B, int R, int Np, int D, void* dpatch_bf16, float* dcls, float* dreg, lp_stream_t stream);
 /* in place: s[r][:n] = softmax(scale * s[r][:n]), s[r][n:ld] = 0   /   dp <- scale * p * (dp - sum(dp * p)) */
 int lp_softmax_rows_fwd(void* s_bf16, int rows, int n, int ld, float scale, lp_stream_t stream);
 int lp_softmax_rows_bwd(const void* p_bf16, void* dp_bf16, int rows, int n, int ld, float scale, lp_stream_t stream);

@@ -72,7 +72,7 @@ AUG_LOCAL_BLUR_COARSE, AUG_LOCAL_EMBOSS = 0, 1
 AUG_ELASTIC_MAX_RADIUS = 20
 TF_NONE, TF_SINGLE, TF_PER_FRAME, TF_PER_VIEW = 0, 1, 2, 3
 
-ABI_VERSION = 149   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
+ABI_VERSION = 150   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -172,6 +172,12 @@ PROTOTYPES = {
     "lp_layernorm_bwd_bf16_colsum": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "lp_layernorm_ls_fwd": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P]),
     "lp_layernorm_ls_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lp_layernorm_ls_fwd_px": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "lp_layernorm_ls_bwd_px": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lp_rope_fwd": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "lp_rope_bwd": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "lp_vit_reg_tokens_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "lp_vit_reg_tokens_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "lp_softmax_rows_fwd": (_I, [_P, _I, _I, _I, _F, _P]),
     "lp_softmax_rows_bwd": (_I, [_P, _P, _I, _I, _I, _F, _P]),
     "lp_transpose_batched": (_I, [_P, _I, _I, _I, C.c_longlong, C.c_longlong, _P, _I, C.c_longlong, C.c_longlong, _I, _I, _P]),
@@ -214,6 +220,12 @@ PROTOTYPES = {
     "lp_f32_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "lp_f32_layernorm_ls_fwd": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P]),
     "lp_f32_layernorm_ls_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lp_f32_layernorm_ls_fwd_px": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "lp_f32_layernorm_ls_bwd_px": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lp_f32_rope_fwd": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "lp_f32_rope_bwd": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "lp_f32_vit_reg_tokens_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "lp_f32_vit_reg_tokens_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "lp_f32_gelu_fwd": (_I, [_P, _Z, _P, _P]),
     "lp_f32_gelu_bwd": (_I, [_P, _P, _Z, _P, _P]),
     "lp_f32_attn_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P]),

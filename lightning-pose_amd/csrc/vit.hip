@@ -132,7 +132,7 @@ __device__ __forceinline__ float mul_then_add(float a, float b, float c) {
 template <int NP, bool LS>
 __device__ __forceinline__ void layernorm_fwd_rows(const float* __restrict__ x, const unsigned short* __restrict__ delta,
                                                    const float* __restrict__ ls, float* __restrict__ x_out, const float* __restrict__ gamma,
-                                                   const float* __restrict__ beta, float eps, int M, int D, int drop_T,
+                                                   const float* __restrict__ beta, float eps, int M, int D, int drop_T, int n_prefix,
                                                    unsigned short* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, hl = lane & 31;
     const int pieces = D >> 2;
@@ -188,8 +188,8 @@ __device__ __forceinline__ void layernorm_fwd_rows(const float* __restrict__ x, 
         bool wy = true;
         if (drop_T > 0) {
             const int b = row / drop_T, t = row - b * drop_T;
-            wy = t > 0;
-            yrow = b * (drop_T - 1) + t - 1;
+            wy = t >= n_prefix;
+            yrow = b * (drop_T - n_prefix) + t - n_prefix;
         }
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
@@ -217,16 +217,16 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
                                                             const float* __restrict__ beta, float eps, int M, int D, int drop_T,
                                                             unsigned short* __restrict__ y, float* __restrict__ mean,
                                                             float* __restrict__ rstd) {
-    layernorm_fwd_rows<NP, false>(x, delta, nullptr, x_out, gamma, beta, eps, M, D, drop_T, y, mean, rstd);
+    layernorm_fwd_rows<NP, false>(x, delta, nullptr, x_out, gamma, beta, eps, M, D, drop_T, 1, y, mean, rstd);
 }
 
 template <int NP>
 __global__ __launch_bounds__(256) void layernorm_ls_fwd_kernel(const float* __restrict__ x, const unsigned short* __restrict__ delta,
                                                                const float* __restrict__ ls, float* __restrict__ x_out,
                                                                const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int M,
-                                                               int D, int drop_T, unsigned short* __restrict__ y, float* __restrict__ mean,
-                                                               float* __restrict__ rstd) {
-    layernorm_fwd_rows<NP, true>(x, delta, ls, x_out, gamma, beta, eps, M, D, drop_T, y, mean, rstd);
+                                                               int D, int drop_T, int n_prefix, unsigned short* __restrict__ y,
+                                                               float* __restrict__ mean, float* __restrict__ rstd) {
+    layernorm_fwd_rows<NP, true>(x, delta, ls, x_out, gamma, beta, eps, M, D, drop_T, n_prefix, y, mean, rstd);
 }
 
 // dx += rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma;  per-workgroup partial d gamma / d beta -> atomics
@@ -240,9 +240,9 @@ template <bool COLSUM, bool LS, int NP>
 __device__ __forceinline__ void layernorm_bwd_rows(const unsigned short* __restrict__ dy, const float* __restrict__ x,
                                                    const float* __restrict__ mean, const float* __restrict__ rstd,
                                                    const float* __restrict__ gamma, const float* __restrict__ ls,
-                                                   const unsigned short* __restrict__ branch, int M, int D, int drop_T, float* __restrict__ dx,
-                                                   unsigned short* __restrict__ dx_bf16, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                   float* __restrict__ colsum, float* __restrict__ dls) {
+                                                   const unsigned short* __restrict__ branch, int M, int D, int drop_T, int n_prefix,
+                                                   float* __restrict__ dx, unsigned short* __restrict__ dx_bf16, float* __restrict__ dgamma,
+                                                   float* __restrict__ dbeta, float* __restrict__ colsum, float* __restrict__ dls) {
     constexpr int kCs = 2, kLs = COLSUM ? 3 : 2;   // rows of `red` behind d gamma, d beta
     __shared__ float red[2 + (COLSUM ? 1 : 0) + (LS ? 1 : 0)][8][128];  // [gamma|beta|column sum|scale][wave, half][column of the current pass]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, hl = lane & 31;
@@ -269,8 +269,8 @@ __device__ __forceinline__ void layernorm_bwd_rows(const unsigned short* __restr
         bool has = live;
         if (drop_T > 0 && live) {
             const int b = row / drop_T, t = row - b * drop_T;
-            has = t > 0;
-            yrow = b * (drop_T - 1) + t - 1;
+            has = t >= n_prefix;
+            yrow = b * (drop_T - n_prefix) + t - n_prefix;
         }
         const float mu = live ? mean[row] : 0.f, rs = live ? rstd[row] : 0.f;
         float g[NP][4], xh[NP][4];
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
                                                             const float* __restrict__ gamma, int M, int D, int drop_T,
                                                             float* __restrict__ dx, unsigned short* __restrict__ dx_bf16,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ colsum) {
-    layernorm_bwd_rows<COLSUM, false, NP>(dy, x, mean, rstd, gamma, nullptr, nullptr, M, D, drop_T, dx, dx_bf16, dgamma, dbeta, colsum, nullptr);
+    layernorm_bwd_rows<COLSUM, false, NP>(dy, x, mean, rstd, gamma, nullptr, nullptr, M, D, drop_T, 1, dx, dx_bf16, dgamma, dbeta, colsum, nullptr);
 }
 
 template <bool COLSUM, int NP>
@@ -369,10 +369,10 @@ __global__ __launch_bounds__(256) void layernorm_ls_bwd_kernel(const unsigned sh
                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                const float* __restrict__ gamma, const float* __restrict__ ls,
                                                                const unsigned short* __restrict__ branch, int M, int D, int drop_T,
-                                                               float* __restrict__ dx, unsigned short* __restrict__ dx_bf16,
+                                                               int n_prefix, float* __restrict__ dx, unsigned short* __restrict__ dx_bf16,
                                                                float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ colsum,
                                                                float* __restrict__ dls) {
-    layernorm_bwd_rows<COLSUM, true, NP>(dy, x, mean, rstd, gamma, ls, branch, M, D, drop_T, dx, dx_bf16, dgamma, dbeta, colsum, dls);
+    layernorm_bwd_rows<COLSUM, true, NP>(dy, x, mean, rstd, gamma, ls, branch, M, D, drop_T, n_prefix, dx, dx_bf16, dgamma, dbeta, colsum, dls);
 }
 
 // ---- GELU (exact, erf) on bf16 streams --------------------------------------------------------------------------------
@@ -743,16 +743,19 @@ extern "C" int lp_layernorm_bwd_bf16_colsum(const void* dy_bf16, const float* x,
 }
 
 // ---- LayerScale inside the two walks (DINOv2): include/lp_hip.h ----------------------------------------------------------------------
-extern "C" int lp_layernorm_ls_fwd(const float* x, const void* delta_bf16, const float* ls, float* x_out, const float* gamma, const float* beta,
-                                   float eps, int M, int D, int drop_T, void* y_bf16, float* mean, float* rstd, lp_stream_t stream) {
+// (`n_prefix` leading rows of every `drop_T` are dropped from y; lp_layernorm_ls_fwd is n_prefix = 1 of the same kernel)
+extern "C" int lp_layernorm_ls_fwd_px(const float* x, const void* delta_bf16, const float* ls, float* x_out, const float* gamma, const float* beta,
+                                      float eps, int M, int D, int drop_T, int n_prefix, void* y_bf16, float* mean, float* rstd,
+                                      lp_stream_t stream) {
     using namespace lp;
-    LP_REQUIRE(x && delta_bf16 && ls && x_out && gamma && beta && y_bf16 && mean && rstd && M > 0 && D > 0 && drop_T >= 0);
+    LP_REQUIRE(x && delta_bf16 && ls && x_out && gamma && beta && y_bf16 && mean && rstd && M > 0 && D > 0 && drop_T >= 0 && n_prefix >= 0 &&
+               (drop_T == 0 || n_prefix <= drop_T));
     if (D > kLnMaxD || D % 4 != 0) return LP_ERR_UNSUPPORTED;
     int blocks = (M + 7) / 8;
     if (blocks > 256 * 8) blocks = 256 * 8;
 #define LP_LN_FWD(NP_)                                                                                                                         \
     hipLaunchKernelGGL((layernorm_ls_fwd_kernel<NP_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (const unsigned short*)delta_bf16, \
-                       ls, x_out, gamma, beta, eps, M, D, drop_T, (unsigned short*)y_bf16, mean, rstd)
+                       ls, x_out, gamma, beta, eps, M, D, drop_T, n_prefix, (unsigned short*)y_bf16, mean, rstd)
     switch ((D + 127) / 128) {
     case 1: LP_LN_FWD(1); break;
     case 2: LP_LN_FWD(2); break;
@@ -765,18 +768,24 @@ extern "C" int lp_layernorm_ls_fwd(const float* x, const void* delta_bf16, const
     return launch_status();
 }
 
-extern "C" int lp_layernorm_ls_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
-                                   const void* branch_bf16, int M, int D, int drop_T, float* dx_acc, void* dx_bf16, float* dgamma_acc,
-                                   float* dbeta_acc, float* colsum_acc, float* dls_acc, lp_stream_t stream) {
+extern "C" int lp_layernorm_ls_fwd(const float* x, const void* delta_bf16, const float* ls, float* x_out, const float* gamma, const float* beta,
+                                   float eps, int M, int D, int drop_T, void* y_bf16, float* mean, float* rstd, lp_stream_t stream) {
+    return lp_layernorm_ls_fwd_px(x, delta_bf16, ls, x_out, gamma, beta, eps, M, D, drop_T, 1, y_bf16, mean, rstd, stream);
+}
+
+extern "C" int lp_layernorm_ls_bwd_px(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                      const float* ls, const void* branch_bf16, int M, int D, int drop_T, int n_prefix, float* dx_acc,
+                                      void* dx_bf16, float* dgamma_acc, float* dbeta_acc, float* colsum_acc, float* dls_acc, lp_stream_t stream) {
     using namespace lp;
     LP_REQUIRE(dy_bf16 && x && mean && rstd && gamma && ls && branch_bf16 && dx_acc && dx_bf16 && dgamma_acc && dbeta_acc && dls_acc && M > 0 &&
-               D > 0 && drop_T >= 0);
+               D > 0 && drop_T >= 0 && n_prefix >= 0 && (drop_T == 0 || n_prefix <= drop_T));
     if (D > kLnMaxD || D % 4 != 0) return LP_ERR_UNSUPPORTED;
     int blocks = (M + 7) / 8;
     if (blocks > 2048) blocks = 2048;  // (as layernorm_bwd_impl)
 #define LP_LN_BWD(CS_, NP_)                                                                                                                      \
     hipLaunchKernelGGL((layernorm_ls_bwd_kernel<CS_, NP_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)dy_bf16, x,  \
-                       mean, rstd, gamma, ls, (const unsigned short*)branch_bf16, M, D, drop_T, dx_acc, (unsigned short*)dx_bf16, dgamma_acc,     \
+                       mean, rstd, gamma, ls, (const unsigned short*)branch_bf16, M, D, drop_T, n_prefix, dx_acc, (unsigned short*)dx_bf16,      \
+                       dgamma_acc,                                                                                                               \
                        dbeta_acc, colsum_acc, dls_acc)
 #define LP_LN_BWD_NP(CS_)                        \
     switch ((D + 127) / 128) {                   \
@@ -795,6 +804,13 @@ extern "C" int lp_layernorm_ls_bwd(const void* dy_bf16, const float* x, const fl
 #undef LP_LN_BWD_NP
 #undef LP_LN_BWD
     return launch_status();
+}
+
+extern "C" int lp_layernorm_ls_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
+                                   const void* branch_bf16, int M, int D, int drop_T, float* dx_acc, void* dx_bf16, float* dgamma_acc,
+                                   float* dbeta_acc, float* colsum_acc, float* dls_acc, lp_stream_t stream) {
+    return lp_layernorm_ls_bwd_px(dy_bf16, x, mean, rstd, gamma, ls, branch_bf16, M, D, drop_T, 1, dx_acc, dx_bf16, dgamma_acc, dbeta_acc,
+                                  colsum_acc, dls_acc, stream);
 }
 
 extern "C" int lp_gelu_fwd(const void* x_bf16, size_t n, void* y_bf16, lp_stream_t stream) {

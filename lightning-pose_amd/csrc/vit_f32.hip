@@ -131,8 +131,8 @@ __device__ __forceinline__ float f32_mul_then_add(float a, float b, float c) {
 __global__ __launch_bounds__(256) void f32_layernorm_ls_fwd_kernel(const float* __restrict__ x, const float* __restrict__ delta,
                                                                    const float* __restrict__ ls, float* __restrict__ x_out,
                                                                    const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                                   int M, int D, int drop_T, float* __restrict__ y, float* __restrict__ mean,
-                                                                   float* __restrict__ rstd) {
+                                                                   int M, int D, int drop_T, int n_prefix, float* __restrict__ y,
+                                                                   float* __restrict__ mean, float* __restrict__ rstd) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
         float* xs = x_out + (size_t)row * D;   // (each lane re-reads what it wrote itself)
@@ -153,29 +153,29 @@ __global__ __launch_bounds__(256) void f32_layernorm_ls_fwd_kernel(const float* 
             mean[row] = mu;
             rstd[row] = rs;
         }
-        if (drop_T > 0 && row % drop_T == 0) continue;
-        const size_t orow = drop_T > 0 ? (size_t)(row - row / drop_T - 1) : (size_t)row;
+        if (drop_T > 0 && row % drop_T < n_prefix) continue;
+        const size_t orow = drop_T > 0 ? (size_t)(row / drop_T) * (drop_T - n_prefix) + (row % drop_T - n_prefix) : (size_t)row;
         for (int d = lane; d < D; d += 64) y[orow * D + d] = fmaf((xs[d] - mu) * rs, gamma[d], beta[d]);
     }
 }
 
 // dx_acc += LayerNorm backward of dy; dx_out = ls o dx_acc; colsum += column sums of dx_out (if wanted); dls += sum_rows dx_acc o branch.
-// Rows without a dy (row % drop_T == 0) leave dx_acc as it is and still contribute to dx_out and to the two sums.
+// Rows without a dy (row % drop_T < n_prefix) leave dx_acc as it is and still contribute to dx_out and to the two sums.
 __global__ __launch_bounds__(256) void f32_layernorm_ls_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                    const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                    const float* __restrict__ gamma, const float* __restrict__ ls,
-                                                                   const float* __restrict__ branch, int M, int D, int drop_T,
+                                                                   const float* __restrict__ branch, int M, int D, int drop_T, int n_prefix,
                                                                    float* __restrict__ dx_acc, float* __restrict__ dx_out,
                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                                    float* __restrict__ colsum, float* __restrict__ dls) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
-        const bool has = !(drop_T > 0 && row % drop_T == 0);   // (wave-uniform)
+        const bool has = !(drop_T > 0 && row % drop_T < n_prefix);   // (wave-uniform)
         const float* xr = x + (size_t)row * D;
         float a = 0.f, b = 0.f, mu = 0.f, rs = 0.f;
         const float* gr = dy;
         if (has) {
-            const size_t orow = drop_T > 0 ? (size_t)(row - row / drop_T - 1) : (size_t)row;
+            const size_t orow = drop_T > 0 ? (size_t)(row / drop_T) * (drop_T - n_prefix) + (row % drop_T - n_prefix) : (size_t)row;
             mu = mean[row];
             rs = rstd[row];
             gr = dy + orow * D;
@@ -397,24 +397,39 @@ extern "C" int lp_f32_layernorm_bwd(const float* dy, const float* x, const float
     return launch_status();
 }
 
+extern "C" int lp_f32_layernorm_ls_fwd_px(const float* x, const float* delta, const float* ls, float* x_out, const float* gamma, const float* beta,
+                                          float eps, int M, int D, int drop_T, int n_prefix, float* y, float* mean, float* rstd,
+                                          lp_stream_t stream) {
+    using namespace lp;
+    LP_REQUIRE(x && delta && ls && x_out && gamma && beta && y && mean && rstd && M > 0 && D > 0 && drop_T >= 0 && n_prefix >= 0 &&
+               (drop_T == 0 || n_prefix <= drop_T));
+    hipLaunchKernelGGL(f32_layernorm_ls_fwd_kernel, dim3(f32_row_grid(M)), dim3(256), 0, (hipStream_t)stream, x, delta, ls, x_out, gamma, beta, eps, M, D, drop_T,
+                       n_prefix, y, mean, rstd);
+    return launch_status();
+}
+
 extern "C" int lp_f32_layernorm_ls_fwd(const float* x, const float* delta, const float* ls, float* x_out, const float* gamma, const float* beta,
                                        float eps, int M, int D, int drop_T, float* y, float* mean, float* rstd, lp_stream_t stream) {
+    return lp_f32_layernorm_ls_fwd_px(x, delta, ls, x_out, gamma, beta, eps, M, D, drop_T, 1, y, mean, rstd, stream);
+}
+
+extern "C" int lp_f32_layernorm_ls_bwd_px(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                          const float* ls, const float* branch, int M, int D, int drop_T, int n_prefix, float* dx_acc,
+                                          float* dx_out, float* dgamma_acc, float* dbeta_acc, float* colsum_acc, float* dls_acc,
+                                          lp_stream_t stream) {
     using namespace lp;
-    LP_REQUIRE(x && delta && ls && x_out && gamma && beta && y && mean && rstd && M > 0 && D > 0 && drop_T >= 0);
-    hipLaunchKernelGGL(f32_layernorm_ls_fwd_kernel, dim3(f32_row_grid(M)), dim3(256), 0, (hipStream_t)stream, x, delta, ls, x_out, gamma, beta, eps, M, D, drop_T, y,
-                       mean, rstd);
+    LP_REQUIRE(dy && x && mean && rstd && gamma && ls && branch && dx_acc && dx_out && dgamma_acc && dbeta_acc && dls_acc && M > 0 && D > 0 &&
+               drop_T >= 0 && n_prefix >= 0 && (drop_T == 0 || n_prefix <= drop_T));
+    hipLaunchKernelGGL(f32_layernorm_ls_bwd_kernel, dim3(f32_row_grid(M)), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, ls, branch, M, D, drop_T,
+                       n_prefix, dx_acc, dx_out, dgamma_acc, dbeta_acc, colsum_acc, dls_acc);
     return launch_status();
 }
 
 extern "C" int lp_f32_layernorm_ls_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* ls,
                                        const float* branch, int M, int D, int drop_T, float* dx_acc, float* dx_out, float* dgamma_acc,
                                        float* dbeta_acc, float* colsum_acc, float* dls_acc, lp_stream_t stream) {
-    using namespace lp;
-    LP_REQUIRE(dy && x && mean && rstd && gamma && ls && branch && dx_acc && dx_out && dgamma_acc && dbeta_acc && dls_acc && M > 0 && D > 0 &&
-               drop_T >= 0);
-    hipLaunchKernelGGL(f32_layernorm_ls_bwd_kernel, dim3(f32_row_grid(M)), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, ls, branch, M, D, drop_T,
-                       dx_acc, dx_out, dgamma_acc, dbeta_acc, colsum_acc, dls_acc);
-    return launch_status();
+    return lp_f32_layernorm_ls_bwd_px(dy, x, mean, rstd, gamma, ls, branch, M, D, drop_T, 1, dx_acc, dx_out, dgamma_acc, dbeta_acc, colsum_acc,
+                                      dls_acc, stream);
 }
 
 extern "C" int lp_f32_gelu_fwd(const float* x, size_t n, float* y, lp_stream_t stream) {

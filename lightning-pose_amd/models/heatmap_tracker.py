@@ -19,10 +19,11 @@ from .. import ops
 from ..data.bboxes import batch_num_views, model_dims, model_to_frame_batch
 from ..engine import Engine
 from ..losses.losses import RegressionRMSELoss
-from .backbones import backbone_features
+from .backbones import tracker_backbone_features
 from .backbones._init import head_state_dict, seeded_state_dict, vit_seeded_state_dict
 from .backbones.dinov2 import dinov2_seeded_state_dict, load_dinov2_checkpoint
-from .backbones.factory import DINOV2_CONFIGS, VIT_CONFIGS
+from .backbones.dinov3 import HF_NAMES as DINOV3_HF_NAMES, dinov3_seeded_state_dict, load_dinov3_checkpoint
+from .backbones.factory import DINOV2_CONFIGS, DINOV3_CONFIGS, VIT_CONFIGS
 from .base import BaseSupervisedTracker, SemiSupervisedTrackerMixin
 from .datatypes import HeatmapTrackerLabeledOutputsDict, HeatmapTrackerUnlabeledOutputsDict
 from .heads.heatmap import HeatmapHead, _Holder
@@ -61,7 +62,7 @@ class HeatmapTracker(BaseSupervisedTracker):
         super().__init__(optimizer=optimizer, optimizer_params=optimizer_params, lr_scheduler=lr_scheduler,
                          lr_scheduler_params=lr_scheduler_params)
         self.backbone_arch = backbone
-        self.num_fc_input_features = backbone_features(backbone)
+        self.num_fc_input_features = tracker_backbone_features(backbone)   # (backbone_features' list + the DINOv3 variants)
         self.do_context = bool(kwargs.get("do_context", False))
         if self.do_context:
             raise NotImplementedError("context (MHCRNN) models are outside the MI355X heatmap-tracker path")
@@ -77,22 +78,34 @@ class HeatmapTracker(BaseSupervisedTracker):
                                 downsample_factor=downsample_factor, _bound=True)
         self.backbone = _Holder()
         checkpoint = kwargs.get("backbone_checkpoint")
-        if backbone in VIT_CONFIGS or backbone in DINOV2_CONFIGS:
+        if backbone in VIT_CONFIGS or backbone in DINOV2_CONFIGS or backbone in DINOV3_CONFIGS:
             from ..vit_engine import ViTEngine
-            dinov2 = backbone not in VIT_CONFIGS
-            hidden, depth, heads, mlp, patch, grid = (DINOV2_CONFIGS if dinov2 else VIT_CONFIGS)[backbone]
+            dinov2, dinov3 = backbone in DINOV2_CONFIGS, backbone in DINOV3_CONFIGS
+            # (the last field: the pretraining grid of the position table; DINOv3 has no table - its register-token count sits there)
+            hidden, depth, heads, mlp, patch, grid = (DINOV3_CONFIGS if dinov3 else DINOV2_CONFIGS if dinov2 else VIT_CONFIGS)[backbone]
             engine_cls = ViTEngine
             if self.precision == "fp32":  # validation mode (vit_engine_fp32.py)
                 from ..vit_engine_fp32 import Fp32ViTEngine as engine_cls
             engine_kwargs, extra_init = self._vit_engine_extras(hidden)
             if dinov2:   # (transformers Dinov2Model: LayerScale, LayerNorm eps 1e-6, its own parameter names - vit_engine.py)
                 engine_kwargs["arch"] = "dinov2"
+            if dinov3:   # (transformers DINOv3ViTModel: rotary positions, register tokens, no key bias - vit_engine.py; the coordinate
+                #  augmentation of training forwards is seeded with the model's seed)
+                engine_kwargs.update(arch="dinov3", registers=grid, rope_seed=torch_seed)
+            else:
+                engine_kwargs["pretrain_grid"] = grid
             self.net = engine_cls(num_keypoints, downsample_factor, device, hidden=hidden, depth=depth, heads=heads, mlp=mlp, patch=patch,
-                                 pretrain_grid=grid, **engine_kwargs)
-            init = (dinov2_seeded_state_dict if dinov2 else vit_seeded_state_dict)(hidden, depth, heads, mlp, patch, grid)
+                                 **engine_kwargs)
+            init = (dinov3_seeded_state_dict if dinov3 else dinov2_seeded_state_dict if dinov2 else vit_seeded_state_dict)(
+                hidden, depth, heads, mlp, patch, grid)
             init.update(head_state_dict(self.num_fc_input_features, num_keypoints, self.head.n_layers))
             init.update(extra_init)
-            if pretrained and dinov2:
+            if pretrained and dinov3:
+                if checkpoint is None:
+                    raise RuntimeError("pretrained=True needs the DINOv3 weights, which cannot be downloaded here; pass backbone_checkpoint="
+                                       f"<state_dict / safetensors file of {DINOV3_HF_NAMES[backbone]}> or pretrained=False")
+                load_dinov3_checkpoint(str(checkpoint), init)
+            elif pretrained and dinov2:
                 if checkpoint is None:
                     raise RuntimeError("pretrained=True needs the DINOv2 weights, which cannot be downloaded here; pass backbone_checkpoint="
                                        "<state_dict / safetensors file of facebook/dinov2-small or dinov2-base> or pretrained=False")

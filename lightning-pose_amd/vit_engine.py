@@ -32,6 +32,7 @@ from .ops import _p
 
 LN_EPS = 1e-12  # ViTConfig.layer_norm_eps
 DINOV2_LN_EPS = 1e-6  # Dinov2Config.layer_norm_eps
+DINOV3_LN_EPS = 1e-5  # DINOv3ViTConfig.layer_norm_eps
 
 
 def bicubic_matrix(n_in: int, n_out: int) -> np.ndarray:
@@ -74,9 +75,9 @@ class LNP:
 
 class ViTPlan:
     def __init__(self, num_keypoints: int, downsample_factor: int, D: int, depth: int, heads: int, mlp: int, patch: int, n_pos: int,
-                 num_views: int = 0, arch: str = "vit"):
+                 num_views: int = 0, arch: str = "vit", registers: int = 0):
         self.D, self.depth, self.heads, self.mlp, self.patch, self.n_pos = D, depth, heads, mlp, patch, n_pos
-        self.arch = arch
+        self.arch, self.registers = arch, registers
         pre = "backbone.vision_encoder"
         off = wd = 0
         # multi-view mode: the (V, D) view embeddings lead the flat buffers.  Their gradient is, with the other embeddings', the LAST to
@@ -107,12 +108,22 @@ class ViTPlan:
         self.cls_off = vec()
         # DINOv2 (transformers Dinov2Model): embeddings.mask_token (1, D), which the forward pass never reads, and per layer the two
         # LayerScale vectors - all inside the backbone's range, each layer's own parameters still one contiguous run (grad_progress)
-        self.mask_off = vec() if arch == "dinov2" else None
+        self.mask_off = vec() if arch in ("dinov2", "dinov3") else None
+        # DINOv3 (transformers DINOv3ViTModel): R register tokens behind [CLS], no position table at all (n_pos = 0), the Conv2d of the patch
+        # embedding without a ``.projection`` level, ``model.layer.{i}`` / ``up_proj`` / ``down_proj`` / ``norm``
+        self.reg_off = off
+        off += registers * D
         self.pos_off = off
         off += n_pos * D
-        self.patch_lin = lin(f"{pre}.embeddings.patch_embeddings.projection", D, 3 * patch * patch)
+        self.patch_lin = lin(f"{pre}.embeddings.patch_embeddings" + ("" if arch == "dinov3" else ".projection"), D, 3 * patch * patch)
         self.layers = []
         for i in range(depth):
+            if arch == "dinov3":
+                p = f"{pre}.model.layer.{i}"
+                self.layers.append(dict(
+                    ln1=ln(f"{p}.norm1"), qkv=lin(f"{p}.attention.qkv", 3 * D, D), proj=lin(f"{p}.attention.o_proj", D, D),
+                    ls1=vec(), ln2=ln(f"{p}.norm2"), fc1=lin(f"{p}.mlp.up_proj", mlp, D), fc2=lin(f"{p}.mlp.down_proj", D, mlp), ls2=vec()))
+                continue
             if arch == "dinov2":
                 p = f"{pre}.encoder.layer.{i}"
                 self.layers.append(dict(
@@ -123,7 +134,7 @@ class ViTPlan:
             self.layers.append(dict(
                 ln1=ln(f"{p}.layernorm_before"), qkv=lin(f"{p}.attention.qkv", 3 * D, D), proj=lin(f"{p}.attention.o_proj", D, D),
                 ln2=ln(f"{p}.layernorm_after"), fc1=lin(f"{p}.mlp.fc1", mlp, D), fc2=lin(f"{p}.mlp.fc2", D, mlp)))
-        self.lnf = ln(f"{pre}.layernorm")
+        self.lnf = ln(f"{pre}.norm" if arch == "dinov3" else f"{pre}.layernorm")
         self.n_backbone = off
         self.head: list[ConvP] = build_head(D, patch, num_keypoints, downsample_factor)
         self.convs: list[ConvP] = list(self.head)
@@ -163,7 +174,16 @@ class ViTEngine(EngineCore):
     a LayerScale on each branch output, LayerNorm eps 1e-6, a ``mask_token`` parameter the forward pass never reads, and that model's
     parameter names.  LayerScale costs no launch: ``lp_layernorm_ls_fwd`` scales the branch output inside the residual add,
     ``lp_layernorm_ls_bwd`` emits the scaled gradient, its column sums and the scale's own gradient; the tape keeps the two
-    unscaled branch outputs of every layer for the latter.  Single-view only."""
+    unscaled branch outputs of every layer for the latter.  Single-view only.
+
+    ``arch="dinov3"`` is transformers' ``DINOv3ViTModel`` ("vits_dinov3" / "vitb_dinov3"): DINOv2's layers (LayerScale, eps 1e-5)
+    with ``registers`` register tokens behind [CLS] (``lp_vit_reg_tokens_*``; the final LayerNorm drops the 1 + R prefix rows,
+    ``lp_layernorm_ls_*_px``), NO position table - the patch tokens' queries and keys are rotated instead (``lp_rope_fwd`` on the fused qkv
+    tensor of every layer, ``lp_rope_bwd`` on its gradient) - and no key bias: the key third of the fused bias vector is a slot that is not a
+    parameter and stays exactly 0.  ``pretrain_grid`` does not apply (there is no table to resize) and must be left unset.  In a training
+    forward the patch coordinates are drawn anew per part of the pass (``pos_embed_shift`` / ``_jitter`` / ``_rescale``, the released
+    configs' rescale 2.0 by default) from the engine's own seeded generator; ``forward(..., rope=draws)`` replays given draws, and
+    ``tape.meta["rope"]`` holds the ones a pass used.  Single-view only."""
 
     # A/B switches (EngineCore.SWITCHES).  bias_fused: every LayerNorm / GELU backward leaves the column sums that are the next Linear
     # layer's bias gradient (0: the weight-gradient launches take them).  gelu_fused: GELU inside fc1's store pass and fc2's data gradient
@@ -171,23 +191,48 @@ class ViTEngine(EngineCore):
     SWITCHES = (("bias_fused", "LP_VIT_BIAS_FUSED", True), ("gelu_fused", "LP_VIT_GELU_FUSED", "1"))
     _patch_dtype = torch.bfloat16
     _token_kernels = ("lp_vit_tokens_fwd", "lp_vit_tokens_bwd", "lp_vit_mv_tokens_fwd", "lp_vit_mv_tokens_bwd")
+    _reg_token_kernels = ("lp_vit_reg_tokens_fwd", "lp_vit_reg_tokens_bwd")
+    _rope_kernels = ("lp_rope_fwd", "lp_rope_bwd")
+    _ln_px_kernels = ("lp_layernorm_ls_fwd_px", "lp_layernorm_ls_bwd_px")
+    _elem_bytes = 2.0    # of a token row's elements (the rope launches' byte counts)
 
     def __init__(self, num_keypoints: int, downsample_factor: int = 2, device: torch.device | str = "cuda:0", hidden: int = 384,
-                 depth: int = 12, heads: int = 6, mlp: int = 1536, patch: int = 16, pretrain_grid: int = 14, num_views: int = 0,
-                 arch: str = "vit"):
+                 depth: int = 12, heads: int = 6, mlp: int = 1536, patch: int = 16, pretrain_grid: int | None = None, num_views: int = 0,
+                 arch: str = "vit", registers: int | None = None, rope_theta: float = 100.0, pos_embed_shift: float | None = None,
+                 pos_embed_jitter: float | None = None, pos_embed_rescale: float | None = 2.0, rope_seed: int = 0):
         if hidden % 64 or (hidden // heads) != 64 or mlp % 64:
             raise NotImplementedError("ViT widths must be multiples of 64 with 64-wide heads (ViT-S/B)")
         if num_views < 0:
             raise ValueError(f"num_views must be positive (0: single-view tokens with [CLS]), got {num_views}")
-        if arch not in ("vit", "dinov2"):
-            raise ValueError(f'arch must be "vit" or "dinov2", got {arch!r}')
-        if arch == "dinov2" and num_views:
-            raise NotImplementedError("the multi-view token assembly (num_views > 0) is not implemented for the DINOv2 backbones")
-        super().__init__(ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, 1 + pretrain_grid * pretrain_grid,
-                                 num_views, arch), num_keypoints, downsample_factor, device)
+        if arch not in ("vit", "dinov2", "dinov3"):
+            raise ValueError(f'arch must be "vit", "dinov2" or "dinov3", got {arch!r}')
+        if arch != "vit" and num_views:
+            raise NotImplementedError("the multi-view token assembly (num_views > 0) is not implemented for the "
+                                      f"{'DINOv2' if arch == 'dinov2' else 'DINOv3'} backbones")
+        if arch == "dinov3":
+            if pretrain_grid is not None:
+                raise ValueError('arch="dinov3" has no position table (its positions are rotary): pretrain_grid does not apply')
+            registers = 4 if registers is None else int(registers)
+            if registers < 0:
+                raise ValueError(f"registers must be >= 0, got {registers}")
+            n_pos, pretrain_grid = 0, 0
+        else:
+            if registers:
+                raise ValueError(f'register tokens belong to arch="dinov3", got registers={registers} with arch={arch!r}')
+            registers = 0
+            pretrain_grid = 14 if pretrain_grid is None else pretrain_grid
+            n_pos = 1 + pretrain_grid * pretrain_grid
+        super().__init__(ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, n_pos, num_views, arch, registers),
+                         num_keypoints, downsample_factor, device)
         self.grid0 = pretrain_grid
         self.arch = arch
-        self.ln_eps = DINOV2_LN_EPS if arch == "dinov2" else LN_EPS
+        self.ln_eps = {"dinov2": DINOV2_LN_EPS, "dinov3": DINOV3_LN_EPS}.get(arch, LN_EPS)
+        # rotary positions (DINOv3): the table of a grid is built on the host with DINOv3ViTRopePositionEmbedding's own torch operations
+        self.rope_theta = float(rope_theta)
+        self.rope_aug = dict(shift=pos_embed_shift, jitter=pos_embed_jitter, rescale=pos_embed_rescale)
+        self._rope_gen = torch.Generator().manual_seed(int(rope_seed))   # (host generator: the draws never touch the device)
+        self._rope_eval: dict[tuple[int, int], torch.Tensor] = {}        # (1, Np, 64) device tables of the plain coordinates, by patch grid
+        self._rope_seq: dict[tuple, torch.Tensor] = {}                   # tab_of_seq arrays, by the part sizes of a pass
         for l in self.plan.norms():
             self.P[l.g_off:l.g_off + hidden] = 1.0
         for L in self.plan.layers:   # (Dinov2Config.layerscale_value = 1.0)
@@ -204,14 +249,19 @@ class ViTEngine(EngineCore):
         sd = {"view_embeddings": buf[pl.view_off:pl.n_view].view(pl.num_views, D)} if pl.num_views else {}
         sd[f"{pre}.embeddings.cls_token"] = buf[pl.cls_off:pl.cls_off + D].view(1, 1, D)
         if pl.mask_off is not None:
-            sd[f"{pre}.embeddings.mask_token"] = buf[pl.mask_off:pl.mask_off + D].view(1, D)
-        sd[f"{pre}.embeddings.position_embeddings"] = buf[pl.pos_off:pl.pos_off + pl.n_pos * D].view(1, pl.n_pos, D)
+            sd[f"{pre}.embeddings.mask_token"] = buf[pl.mask_off:pl.mask_off + D].view(*((1, 1, D) if pl.arch == "dinov3" else (1, D)))
+        if pl.arch == "dinov3":
+            sd[f"{pre}.embeddings.register_tokens"] = buf[pl.reg_off:pl.reg_off + pl.registers * D].view(1, pl.registers, D)
+        else:
+            sd[f"{pre}.embeddings.position_embeddings"] = buf[pl.pos_off:pl.pos_off + pl.n_pos * D].view(1, pl.n_pos, D)
         for l in pl.linears():
             w, b = buf[l.w_off:l.w_off + l.N * l.K], buf[l.b_off:l.b_off + l.N]
             if l.name.endswith("attention.qkv"):  # fused [q; k; v]: three reference parameters share one GEMM weight
                 stem = l.name[:-len("qkv")]
                 for j, nm in enumerate(("query", "key", "value") if pl.arch == "dinov2" else ("q_proj", "k_proj", "v_proj")):
                     sd[f"{stem}{nm}.weight"] = w[j * D * D:(j + 1) * D * D].view(D, D)
+                    if pl.arch == "dinov3" and j == 1:
+                        continue   # key_bias=False: that third of the fused bias vector is a slot, not a parameter - it stays 0 (_clear_key_bias)
                     sd[f"{stem}{nm}.bias"] = b[j * D:(j + 1) * D]
             elif l is pl.patch_lin:
                 sd[f"{l.name}.weight"] = w.view(D, 3, pl.patch, pl.patch)
@@ -222,10 +272,11 @@ class ViTEngine(EngineCore):
         for l in pl.norms():
             sd[f"{l.name}.weight"] = buf[l.g_off:l.g_off + D]
             sd[f"{l.name}.bias"] = buf[l.b_off:l.b_off + D]
-        if pl.arch == "dinov2":
+        if pl.arch in ("dinov2", "dinov3"):
+            layer = "encoder.layer" if pl.arch == "dinov2" else "model.layer"
             for i, L in enumerate(pl.layers):
                 for nm in ("1", "2"):
-                    sd[f"{pre}.encoder.layer.{i}.layer_scale{nm}.lambda1"] = buf[L["ls" + nm]:L["ls" + nm] + D]
+                    sd[f"{pre}.{layer}.{i}.layer_scale{nm}.lambda1"] = buf[L["ls" + nm]:L["ls" + nm] + D]
         sd.update(self._head_views(buf))
         return sd
 
@@ -249,7 +300,7 @@ class ViTEngine(EngineCore):
 
     @torch.no_grad()
     def load_state_dict(self, sd: dict[str, torch.Tensor], strict: bool = True) -> None:
-        if self.arch != "dinov2":   # (Dinov2Model's own names are the 4.x-style ones: nothing to translate)
+        if self.arch == "vit":   # (Dinov2Model's own names are the 4.x-style ones, DINOv3ViTModel's are its own: nothing to translate)
             sd = {self.canonical_key(k): v for k, v in sd.items()}
         EngineCore.load_state_dict(self, sd, strict)
 
@@ -330,14 +381,21 @@ class ViTEngine(EngineCore):
                     nbytes=2.0 * (M * l.K + M * l.N + l.N * l.K))
         return dx
 
-    def _ln(self, x, delta, l: LNP, M: int, drop_T: int = 0, ls: int | None = None):
-        """``ls``: offset of the LayerScale vector that scales ``delta`` in front of the residual add (DINOv2)"""
+    def _ln(self, x, delta, l: LNP, M: int, drop_T: int = 0, ls: int | None = None, n_prefix: int = 1):
+        """``ls``: offset of the LayerScale vector that scales ``delta`` in front of the residual add (DINOv2, DINOv3);
+        ``n_prefix``: leading rows of every ``drop_T`` that do not reach y ([CLS]; DINOv3: [CLS] and the registers)"""
         D = self.plan.D
         xo = torch.empty_like(x) if delta is not None else None
-        rows = M - M // drop_T if drop_T else M
+        rows = M - (M // drop_T) * n_prefix if drop_T else M
         y = torch.empty(rows, D, device=self.device, dtype=torch.bfloat16)
         mean = torch.empty(M, device=self.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
+        if drop_T and n_prefix != 1:   # (only the LayerScale walk has the prefix-taking form: every model with registers has LayerScale)
+            assert ls is not None and delta is not None
+            fwd = self._ln_px_kernels[0]
+            check(getattr(self._lib, fwd)(_p(x), _p(delta), _p(self.P[ls:]), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]), self.ln_eps, M, D,
+                                          drop_T, n_prefix, _p(y), _p(mean), _p(rstd), ops._stream()), fwd)
+            return y, mean, rstd, xo
         if ls is not None and delta is not None:
             check(self._lib.lp_layernorm_ls_fwd(_p(x), _p(delta), _p(self.P[ls:]), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]), self.ln_eps,
                                                 M, D, drop_T, _p(y), _p(mean), _p(rstd), ops._stream()), "lp_layernorm_ls_fwd")
@@ -347,11 +405,19 @@ class ViTEngine(EngineCore):
         return y, mean, rstd, (xo if xo is not None else x)
 
     def _ln_bwd(self, dy, x, mean, rstd, l: LNP, M: int, dx, drop_T: int = 0, want_bf16: bool = False, colsum: torch.Tensor | None = None,
-                ls: int | None = None, branch: torch.Tensor | None = None):
+                ls: int | None = None, branch: torch.Tensor | None = None, n_prefix: int = 1):
         """dx (fp32, the residual stream's gradient) += LayerNorm backward of dy; ``want_bf16``: also return the updated dx in bf16;
         ``colsum``: accumulate that bf16 tensor's column sums there (the bias gradient of the Linear layer it is the dy of);
         ``ls`` / ``branch`` (DINOv2): the returned tensor feeds a branch through the LayerScale vector at offset ``ls`` - it leaves scaled, and
         the scale's gradient (against ``branch``, that branch's unscaled forward output) is accumulated into G"""
+        if drop_T and n_prefix != 1:
+            assert want_bf16 and ls is not None
+            bwd = self._ln_px_kernels[1]
+            out = torch.empty(M, self.plan.D, device=self.device, dtype=torch.bfloat16)
+            check(getattr(self._lib, bwd)(_p(dy), _p(x), _p(mean), _p(rstd), _p(self.P[l.g_off:]), _p(self.P[ls:]), _p(branch), M, self.plan.D,
+                                          drop_T, n_prefix, _p(dx), _p(out), _p(self.G[l.g_off:]), _p(self.G[l.b_off:]), _p(colsum),
+                                          _p(self.G[ls:]), ops._stream()), bwd)
+            return out
         if want_bf16 and ls is not None:
             out = torch.empty(M, self.plan.D, device=self.device, dtype=torch.bfloat16)
             check(self._lib.lp_layernorm_ls_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _p(self.P[l.g_off:]), _p(self.P[ls:]), _p(branch), M, self.plan.D,
@@ -393,20 +459,100 @@ class ViTEngine(EngineCore):
               "lp_small_matmul")
         return out
 
+    # ------------------------------------------------------------------------------------------------ rotary positions (DINOv3)
+    def rope_draw(self) -> dict[str, torch.Tensor]:
+        """One draw of the training-mode coordinate augmentation (transformers ``augment_patches_center_coordinates``: a shift per axis, a
+        log-uniform factor per axis, one log-uniform factor) from the engine's generator, as float32 host tensors; only the knobs that are set"""
+        a, g, d = self.rope_aug, self._rope_gen, {}
+        if a["shift"] is not None:
+            d["shift"] = torch.empty(1, 2).uniform_(-a["shift"], a["shift"], generator=g)
+        if a["jitter"] is not None:
+            r = float(np.log(a["jitter"]))
+            d["jitter"] = torch.empty(1, 2).uniform_(-r, r, generator=g).exp()
+        if a["rescale"] is not None:
+            r = float(np.log(a["rescale"]))
+            d["rescale"] = torch.empty(1).uniform_(-r, r, generator=g).exp()
+        return d
+
+    def rope_table_host(self, gh: int, gw: int, draw: dict[str, torch.Tensor] | None = None) -> torch.Tensor:
+        """(gh * gw, 64) float32 on the host, per patch cos[0:32] | sin[0:32]: the 32 distinct columns of DINOv3ViTRopePositionEmbedding's
+        (cos, sin), computed with its own torch operations in its own order (patch centres in [-1, 1], the draw's shift / jitter / rescale,
+        angle = 2 pi * coordinate * inv_freq, [y angles | x angles]) - without a draw it is bit-equal to the HF module's eval output"""
+        hd = self.plan.D // self.plan.heads
+        inv_freq = 1 / self.rope_theta ** torch.arange(0, 1, 4 / hd, dtype=torch.float32)
+        ch = torch.arange(0.5, gh, dtype=torch.float32) / gh
+        cw = torch.arange(0.5, gw, dtype=torch.float32) / gw
+        coords = 2.0 * torch.stack(torch.meshgrid(ch, cw, indexing="ij"), dim=-1).flatten(0, 1) - 1.0
+        if draw:
+            if draw.get("shift") is not None:
+                coords = coords + draw["shift"]
+            if draw.get("jitter") is not None:
+                coords = coords * draw["jitter"]
+            if draw.get("rescale") is not None:
+                coords = coords * draw["rescale"]
+        angles = (2 * math.pi * coords[:, :, None] * inv_freq[None, None, :]).flatten(1, 2)
+        return torch.cat((torch.cos(angles), torch.sin(angles)), dim=1).contiguous()
+
+    def _rope_tables(self, gh: int, gw: int, sizes: list[int], training: bool, rope):
+        """(device table (n_tab, Np, 64), tab_of_seq or None, n_tab, the draws or None) of a pass over batches of ``sizes`` images: the cached
+        plain table, or - a training forward with a knob set, or draws to replay - one table per part, built on the host and copied without
+        blocking; nothing is read back"""
+        if self.arch != "dinov3":
+            return None, None, 0, None
+        if rope is None and not (training and any(v is not None for v in self.rope_aug.values())):
+            if (gh, gw) not in self._rope_eval:
+                self._rope_eval[(gh, gw)] = self.rope_table_host(gh, gw)[None].to(self.device)
+            return self._rope_eval[(gh, gw)], None, 1, None
+        draws = [self.rope_draw() for _ in sizes] if rope is None else list(rope)
+        if len(draws) != len(sizes):
+            raise ValueError(f"rope= holds {len(draws)} draws for a pass of {len(sizes)} part(s)")
+        host = torch.stack([self.rope_table_host(gh, gw, d) for d in draws])
+        key = tuple(sizes)
+        if key not in self._rope_seq:
+            self._rope_seq[key] = torch.tensor([i for i, n in enumerate(sizes) for _ in range(n)], dtype=torch.int32).to(self.device)
+        if self.device.type == "cuda":
+            host = host.pin_memory()
+        return host.to(self.device, non_blocking=True), self._rope_seq[key], len(draws), draws
+
+    def _rope(self, bwd: int, t: torch.Tensor, ld: int, tab: torch.Tensor, seq: torch.Tensor | None, n_tab: int, Bs: int, Tn: int) -> None:
+        """rotate the Q and K columns of the patch rows of the fused (M, 3 D) tensor ``t`` in place (``bwd``: the transposed rotation)"""
+        D, nh, name = self.plan.D, self.plan.heads, self._rope_kernels[bwd]
+        n = float(Bs * (Tn - self.n_prefix) * 2 * D)      # elements rotated: 2 products + 1 sum each, read once and written once
+        self._timed(name, 3.0 * n, lambda: check(getattr(self._lib, name)(
+            _p(t), ld, D, _p(tab), _p(seq), n_tab, Bs, Tn, self.n_prefix, nh, D // nh, ops._stream()), name), nbytes=2.0 * n * self._elem_bytes)
+
+    def _clear_key_bias(self, l: Lin) -> None:
+        """DINOv3 has no key bias: the key third of the fused bias vector is not a parameter.  Under the rotation a key bias would NOT be
+        invisible to the soft-max, so the column sums the weight-gradient pass leaves there are non-zero - cleared here, before the layer's
+        gradients are announced (grad_progress), so that the optimiser leaves the slot at exactly 0"""
+        if self.wgrad_side_stream:
+            self._join_side_stream()
+        D = self.plan.D
+        self.G[l.b_off + D:l.b_off + 2 * D].zero_()
+
     # ------------------------------------------------------------------------------------------------ tokens
     def _seq(self, parts: list[torch.Tensor], Np: int) -> tuple[int, int, int]:
         """(sequences, tokens per sequence, ``drop_T`` of the final LayerNorm) for these batches of images with Np patches each"""
         V = self.plan.num_views
         B = sum(p_.shape[0] for p_ in parts)
-        if not V:
-            return B, Np + 1, Np + 1            # one sequence per image, [CLS] in front and dropped in front of the head
+        if not V:   # one sequence per image, [CLS] (and DINOv3's registers: self.n_prefix rows) in front and dropped in front of the head
+            return B, Np + self.n_prefix, Np + self.n_prefix
         if any(p_.shape[0] % V for p_ in parts):
             raise ValueError(f"a multi-view batch holds num_views = {V} images per sample, got {[p_.shape[0] for p_ in parts]} images")
         return B // V, V * Np, 0                # one sequence per sample: the patches of all its views, nothing dropped
 
-    def _tokens_fwd(self, pe: torch.Tensor, pos: torch.Tensor, B: int, Np: int, x: torch.Tensor) -> None:
+    @property
+    def n_prefix(self) -> int:
+        """rows in front of the patch tokens of a single-view sequence: [CLS] and the register tokens"""
+        return 1 + self.plan.registers
+
+    def _tokens_fwd(self, pe: torch.Tensor, pos: torch.Tensor | None, B: int, Np: int, x: torch.Tensor) -> None:
         pl, (fwd, _, mv_fwd, _) = self.plan, self._token_kernels
-        if pl.num_views:
+        if pl.arch == "dinov3":   # [CLS], the registers, the patch embeddings: nothing is added to the tokens
+            fwd = self._reg_token_kernels[0]
+            check(getattr(self._lib, fwd)(_p(pe), _p(self.P[pl.cls_off:]), _p(self.P[pl.reg_off:]) if pl.registers else None, B, pl.registers, Np,
+                                          pl.D, _p(x), ops._stream()), fwd)
+        elif pl.num_views:
             V = pl.num_views
             check(getattr(self._lib, mv_fwd)(_p(pe), _p(pos), _p(self.P[pl.view_off:]), B // V, V, Np, pl.D, _p(x), ops._stream()), mv_fwd)
         else:
@@ -418,6 +564,14 @@ class ViTEngine(EngineCore):
         pl, D, dev = self.plan, self.plan.D, self.device
         _, bwd, _, mv_bwd = self._token_kernels
         dpatch = torch.empty(B * Np, D, device=dev, dtype=self._patch_dtype)
+        if pl.arch == "dinov3":   # the kernel WRITES the sums over the images; they are added to G here (a backward pass accumulates)
+            R, bwd = pl.registers, self._reg_token_kernels[1]
+            dpre = torch.empty(1 + R, D, device=dev, dtype=torch.float32)
+            check(getattr(self._lib, bwd)(_p(dx), B, R, Np, D, _p(dpatch), _p(dpre), _p(dpre[1:]) if R else None, ops._stream()), bwd)
+            self.G[pl.cls_off:pl.cls_off + D] += dpre[0]
+            if R:
+                self.G[pl.reg_off:pl.reg_off + R * D] += dpre[1:].reshape(-1)
+            return dpatch
         dpos = torch.empty(Np + 1, D, device=dev, dtype=torch.float32)
         gpos = self.G[pl.pos_off:pl.pos_off + pl.n_pos * D].view(pl.n_pos, D)
         if pl.num_views:   # no [CLS] row: cls_token and gpos[0] keep their zero gradient
@@ -443,16 +597,17 @@ class ViTEngine(EngineCore):
         """no batch statistics anywhere (LayerNorm is per token): two batches of equally sized images always share one pass"""
         return n0 > 0
 
-    def forward(self, images, training: bool = True) -> tuple[torch.Tensor, Tape]:
-        """``images``: a tensor, or a pair (labeled, unlabeled frames) that runs as one batch"""
-        return self._forward(images, training, keep=True)
+    def forward(self, images, training: bool = True, rope=None) -> tuple[torch.Tensor, Tape]:
+        """``images``: a tensor, or a pair (labeled, unlabeled frames) that runs as one batch.  ``rope`` (DINOv3): the coordinate draws to
+        use, one dict per part as ``tape.meta["rope"]`` holds them, instead of new ones"""
+        return self._forward(images, training, keep=True, rope=rope)
 
     def forward_infer(self, images: torch.Tensor) -> torch.Tensor:
         """Inference forward (predict_step under eval + no_grad): the attention probabilities are never written (lp_attn_fwd with
         p = NULL drops the 2 x 0.85 GB per layer the training pass stores for its backward) and no tape is kept."""
         return self._forward(images, False, keep=False)[0]
 
-    def _forward(self, images, training: bool, keep: bool) -> tuple[torch.Tensor, Tape]:
+    def _forward(self, images, training: bool, keep: bool, rope=None) -> tuple[torch.Tensor, Tape]:
         pl = self.plan
         D, nh, pt = pl.D, pl.heads, pl.patch
         parts, B, H, W = image_parts(images, pt, None, of="the patch size ")
@@ -472,16 +627,21 @@ class ViTEngine(EngineCore):
             i0 += p_.shape[0]
         pe = self._linear(patches, pl.patch_lin, B * Np)
         x = torch.empty(M, D, device=dev, dtype=torch.float32)
-        pos = self._pos(gh, gw)  # (kept alive across the launch)
+        pos = self._pos(gh, gw) if pl.n_pos else None  # (kept alive across the launch)
         self._tokens_fwd(pe, pos, B, Np, x)
+        rope_tab, rope_seq, n_tab, draws = self._rope_tables(gh, gw, [p_.shape[0] for p_ in parts], training, rope)
         if keep:
             T["patches"] = patches
+            if rope_tab is not None:
+                T["rope_tab"], T["rope_seq"] = rope_tab, rope_seq
         delta = None
         scale = 1.0 / math.sqrt(D // nh)
         qs = 3 * D  # row pitch of the fused qkv tensor
         for i, L in enumerate(pl.layers):
             y1, m1, r1, x = self._ln(x, delta, L["ln1"], M, ls=pl.layers[i - 1].get("ls2") if i else None)
             qkv = self._linear(y1, L["qkv"], M)
+            if rope_tab is not None:   # DINOv3: the patch tokens' q and k rotated in place; the tape keeps the rotated q and k, which is
+                self._rope(0, qkv, qs, rope_tab, rope_seq, n_tab, Bs, Tn)   # what lp_attn_bwd_kv and dQ = dS K need
             # P = softmax(Q K^T / 8) (bf16, row pitch Tp, pad columns zero; kept for the backward pass) and attn = P V in one kernel:
             # the scores themselves never reach memory
             S = torch.empty(Bs * nh * Tn, Tp, device=dev, dtype=torch.bfloat16) if keep else None
@@ -501,11 +661,11 @@ class ViTEngine(EngineCore):
                     T[f"l{i}.{nm}"] = v
                 if "ls1" in L:   # the unscaled branch outputs: the LayerScale gradients are taken against them
                     T[f"l{i}.proj"], T[f"l{i}.fc2"] = proj, delta
-        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"))
+        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"), n_prefix=self.n_prefix)
         if keep:
             T["x_last"], T["mf"], T["rf"] = x, mf, rf
         heat = self._head_forward(feat.view(B, gh, gw, D), B, gh, gw, T if keep else {})
-        tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training, seq=(Bs, Tn, drop_T))
+        tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training, seq=(Bs, Tn, drop_T), rope=draws)
         return heat, tp
 
     # ------------------------------------------------------------------------------------------------ backward
@@ -539,7 +699,8 @@ class ViTEngine(EngineCore):
             return dict(ls=pl.layers[j]["ls" + nm], branch=T[f"l{j}." + ("proj" if nm == "1" else "fc2")])
 
         dx16 = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, colsum=bsum(pl.layers[-1]["fc2"]),
-                            **scaled(pl.depth - 1, "2"))
+                            n_prefix=self.n_prefix, **scaled(pl.depth - 1, "2"))
+        rope_tab, rope_seq = T.get("rope_tab"), T.get("rope_seq")
 
         for i in range(pl.depth - 1, -1, -1):
             L = pl.layers[i]
@@ -586,7 +747,11 @@ class ViTEngine(EngineCore):
             self._gemm(_p(dS), Tp, _p(tmpT), Tp, Tn, 64, Tp, dqkv, qs, batch=(Bs, nh, *zP, *zT, Tn * qs, 64))
             if trace is not None:
                 trace[f"l{i}.dqkv"] = dqkv
+            if rope_tab is not None:   # dqkv is complete: the transposed rotation of dQ / dK, before the qkv weight gradient reads it
+                self._rope(1, dqkv, qs, rope_tab, rope_seq, rope_tab.shape[0], Bs, Tn)
             d_y1 = self._linear_bwd(L["qkv"], t("y1"), dqkv, M)
+            if pl.arch == "dinov3":
+                self._clear_key_bias(L["qkv"])
             dx16 = self._ln_bwd(d_y1, t("x_in"), t("m1"), t("r1"), L["ln1"], M, dx, want_bf16=i > 0,
                                 colsum=bsum(pl.layers[i - 1]["fc2"]) if i > 0 else None, **(scaled(i - 1, "2") if i > 0 else {}))
             if progress is not None:

@@ -28,6 +28,10 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
 
     _patch_dtype = torch.float32
     _token_kernels = ("lp_f32_vit_tokens_fwd", "lp_f32_vit_tokens_bwd", "lp_f32_vit_mv_tokens_fwd", "lp_f32_vit_mv_tokens_bwd")
+    _reg_token_kernels = ("lp_f32_vit_reg_tokens_fwd", "lp_f32_vit_reg_tokens_bwd")
+    _rope_kernels = ("lp_f32_rope_fwd", "lp_f32_rope_bwd")
+    _ln_px_kernels = ("lp_f32_layernorm_ls_fwd_px", "lp_f32_layernorm_ls_bwd_px")
+    _elem_bytes = 4.0
 
     @staticmethod
     def _lin_geom(l: Lin, M: int):
@@ -52,12 +56,18 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
               "lp_f32_conv_dgrad(linear)")
         return dx
 
-    def _ln(self, x, delta, l: LNP, M: int, drop_T: int = 0, ls: int | None = None):
+    def _ln(self, x, delta, l: LNP, M: int, drop_T: int = 0, ls: int | None = None, n_prefix: int = 1):
         D = self.plan.D
         xo = torch.empty_like(x) if delta is not None else None
-        rows = M - M // drop_T if drop_T else M
+        rows = M - (M // drop_T) * n_prefix if drop_T else M
         y = self._f32(rows, D)
         mean, rstd = self._f32(M), self._f32(M)
+        if drop_T and n_prefix != 1:   # DINOv3: [CLS] and the registers dropped (the LayerScale walk's prefix-taking form)
+            assert ls is not None and delta is not None
+            check(self._lib.lp_f32_layernorm_ls_fwd_px(_p(x), _p(delta), _p(self.P[ls:]), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]),
+                                                       self.ln_eps, M, D, drop_T, n_prefix, _p(y), _p(mean), _p(rstd), ops._stream()),
+                  "lp_f32_layernorm_ls_fwd_px")
+            return y, mean, rstd, xo
         if ls is not None and delta is not None:   # DINOv2: x_out = x + (delta * LayerScale)
             check(self._lib.lp_f32_layernorm_ls_fwd(_p(x), _p(delta), _p(self.P[ls:]), _p(xo), _p(self.P[l.g_off:]), _p(self.P[l.b_off:]),
                                                     self.ln_eps, M, D, drop_T, _p(y), _p(mean), _p(rstd), ops._stream()), "lp_f32_layernorm_ls_fwd")
@@ -66,7 +76,15 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
                                              _p(mean), _p(rstd), ops._stream()), "lp_f32_layernorm_fwd")
         return y, mean, rstd, (xo if xo is not None else x)
 
-    def _ln_bwd(self, dy, x, mean, rstd, l: LNP, M: int, dx, drop_T: int = 0, want_bf16: bool = False, ls: int | None = None, branch=None):
+    def _ln_bwd(self, dy, x, mean, rstd, l: LNP, M: int, dx, drop_T: int = 0, want_bf16: bool = False, ls: int | None = None, branch=None,
+                n_prefix: int = 1):
+        if drop_T and n_prefix != 1:
+            assert want_bf16 and ls is not None
+            out = self._f32(M, self.plan.D)
+            check(self._lib.lp_f32_layernorm_ls_bwd_px(_p(dy), _p(x), _p(mean), _p(rstd), _p(self.P[l.g_off:]), _p(self.P[ls:]), _p(branch), M,
+                                                       self.plan.D, drop_T, n_prefix, _p(dx), _p(out), _p(self.G[l.g_off:]), _p(self.G[l.b_off:]),
+                                                       None, _p(self.G[ls:]), ops._stream()), "lp_f32_layernorm_ls_bwd_px")
+            return out
         if want_bf16 and ls is not None:   # DINOv2: the operand of the next Linear backward leaves through the LayerScale at offset ``ls``
             out = self._f32(M, self.plan.D)
             check(self._lib.lp_f32_layernorm_ls_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _p(self.P[l.g_off:]), _p(self.P[ls:]), _p(branch), M,
@@ -77,7 +95,7 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
                                              _p(self.G[l.g_off:]), _p(self.G[l.b_off:]), ops._stream()), "lp_f32_layernorm_bwd")
         return dx.clone() if want_bf16 else None   # (the operand of the next Linear backward: dx itself moves on in place)
 
-    def _forward(self, images, training: bool, keep: bool):
+    def _forward(self, images, training: bool, keep: bool, rope=None):
         pl = self.plan
         D, nh, pt = pl.D, pl.heads, pl.patch
         parts, B, H, W = image_parts(images, pt, None, of="the patch size ")
@@ -94,15 +112,20 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
             i0 += p_.shape[0]
         pe = self._linear(patches, pl.patch_lin, B * Np)
         x = self._f32(M, D)
-        pos = self._pos(gh, gw)
+        pos = self._pos(gh, gw) if pl.n_pos else None
         self._tokens_fwd(pe, pos, B, Np, x)
         T["patches"] = patches
+        rope_tab, rope_seq, n_tab, draws = self._rope_tables(gh, gw, [p_.shape[0] for p_ in parts], training, rope)
+        if rope_tab is not None:
+            T["rope_tab"], T["rope_seq"] = rope_tab, rope_seq
         delta = None
         scale = 1.0 / math.sqrt(D // nh)
         qs = 3 * D
         for i, L in enumerate(pl.layers):
             y1, m1, r1, x = self._ln(x, delta, L["ln1"], M, ls=pl.layers[i - 1].get("ls2") if i else None)
             qkv = self._linear(y1, L["qkv"], M)
+            if rope_tab is not None:   # DINOv3: the patch tokens' q and k rotated in place (the tape keeps them rotated)
+                self._rope(0, qkv, qs, rope_tab, rope_seq, n_tab, Bs, Tn)
             Pm = self._f32(Bs * nh * Tn, Tn)
             attn = self._f32(M, D)
             check(self._lib.lp_f32_attn_fwd(_p(qkv), qs, D, 2 * D, Bs, nh, Tn, scale, _p(Pm), _p(attn), D, ops._stream()), "lp_f32_attn_fwd")
@@ -119,10 +142,10 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
                     T[f"l{i}.{nm}"] = v
                 if "ls1" in L:   # the unscaled branch outputs: the LayerScale gradients are taken against them
                     T[f"l{i}.proj"], T[f"l{i}.fc2"] = proj, delta
-        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"))
+        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"), n_prefix=self.n_prefix)
         T["x_last"], T["mf"], T["rf"] = x, mf, rf
         heat = self._head_forward(feat.view(B, gh, gw, D), B, gh, gw, T)
-        tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training, seq=(Bs, Tn, drop_T))
+        tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training, seq=(Bs, Tn, drop_T), rope=draws)
         return heat, tp
 
     def backward(self, tp: Tape, g_heat: torch.Tensor, trace: dict | None = None) -> None:
@@ -142,7 +165,9 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
                 return {}
             return dict(ls=pl.layers[j]["ls" + nm], branch=T[f"l{j}." + ("proj" if nm == "1" else "fc2")])
 
-        dcur = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, **scaled(pl.depth - 1, "2"))
+        dcur = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, n_prefix=self.n_prefix,
+                            **scaled(pl.depth - 1, "2"))
+        rope_tab, rope_seq = T.get("rope_tab"), T.get("rope_seq")
         for i in range(pl.depth - 1, -1, -1):
             L = pl.layers[i]
             t = lambda nm: T[f"l{i}.{nm}"]  # noqa: E731
@@ -160,7 +185,11 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
                                             ops._stream()), "lp_f32_attn_bwd")
             if trace is not None:
                 trace[f"l{i}.dqkv"] = dqkv
+            if rope_tab is not None:   # the transposed rotation of dQ / dK, before the qkv weight gradient reads them
+                self._rope(1, dqkv, qs, rope_tab, rope_seq, rope_tab.shape[0], Bs, Tn)
             d_y1 = self._linear_bwd(L["qkv"], t("y1"), dqkv, M)
+            if pl.arch == "dinov3":
+                self._clear_key_bias(L["qkv"])
             dcur = self._ln_bwd(d_y1, t("x_in"), t("m1"), t("r1"), L["ln1"], M, dx, want_bf16=i > 0, **(scaled(i - 1, "2") if i > 0 else {}))
         if trace is not None:
             trace["tokens.dx"] = dx

@@ -23,7 +23,9 @@ HOT = ("lp::conv_pipe_kernel", "lp::conv_spec_kernel", "lp::conv_wgrad_pipe_kern
        "lp::hm_rowsq_kernel", "lp::hm_grad_kernel", "lp::softmax2d", "lp::adam_kernel", "lp::pca_kernel", "lp::temporal_kernel",
        "lp::attn_fwd_kernel", "lp::attn_bwd_kv_kernel", "lp::pixel_shuffle",
        # the DINOv2 step's LayerNorm walks: four per-lane accumulator arrays at NP = 6 (ViT-B) must stay in registers
-       "lp::layernorm_ls_fwd_kernel", "lp::layernorm_ls_bwd_kernel")
+       "lp::layernorm_ls_fwd_kernel", "lp::layernorm_ls_bwd_kernel",
+       # the DINOv3 step: the rotation of q / k (24 launches per step) and the token assembly with registers
+       "lp::rope_kernel", "lp::vit_reg_tokens_fwd_kernel", "lp::vit_reg_tokens_bwd_kernel")
 # decode_bwd_kernel<R, TY, NE = 64, ...> is the catch-all instantiation for maps larger than any BASELINE config selects (ne > 18 elements per
 # thread: heat-maps above 96 x 96 at 512 threads); it keeps its element array in scratch by design
 ALLOWED_SCRATCH = (
