@@ -53,8 +53,9 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * 144 = the multi-view token assembly (lp_vit_mv_tokens_*), 145 = the camera geometry of the calibrated 3-D losses (lp_cam_*),
  * 146 = patch masking (lp_patch_mask_f32), 147 = LayerScale inside the LayerNorm walks (lp_layernorm_ls_*, the DINOv2 backbones),
  * 148 = the multi-view labeled batch with its 3-D augmentation (lp_mv3d_*), 149 = lp_conv_last_resident,
- * 150 = the DINOv3 backbones: lp_rope_*, lp_vit_reg_tokens_*, the prefix-dropping lp_layernorm_ls_*_px (and their fp32 forms). */
-#define LP_HIP_ABI_VERSION 150
+ * 150 = the DINOv3 backbones: lp_rope_*, lp_vit_reg_tokens_*, the prefix-dropping lp_layernorm_ls_*_px (and their fp32 forms),
+ * 151 = crop-zoom prediction: lp_bbox_from_keypoints, lp_bbox_smooth, lp_frames_crop_resize. */
+#define LP_HIP_ABI_VERSION 151
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -704,6 +705,34 @@ int lp_frames_augment(const float* src_hwc, int S, int H, int W, const lp_frame_
 int lp_labeled_keypoints(const float* kp_src, const float* src_hw, const float* affine, const int* hflip, const int* swap,
                          const int* vis_in, int uniform_heatmaps, int B, int K, int H, int W, float* kp_out, int* vis_out,
                          lp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Crop-zoom prediction (csrc/cropzoom.hip; reference utils/cropzoom.py): a detector's keypoints -> one box per frame -> [rolling median] ->
+ * each frame's own region of interest resampled from the uint8 frame into the pose model's input planes.  The boxes stay in device memory
+ * from the first call to the last; no call reads anything back.
+ * ------------------------------------------------------------------------------------------------------ */
+enum { LP_BBOX_MAX_ANCHORS = 64,        /* anchor indices travel as kernel arguments (bytes: K <= 256 when a list is given)          */
+       LP_BBOX_SMOOTH_MAX_WINDOW = 255  /* the median is found by counting ranks: window^2 comparisons per frame and column        */ };
+
+/* keypoints (N, K, 2) fp32 frame px -> bbox (N, 4) int32 [x, y, h, w]: _compute_bbox_df / _calculate_bbox_size (utils/cropzoom.py:31-143) in
+ * double precision with the sums taken in keypoint order.  `anchors` is a HOST array of n_anchors keypoint indices (0: every keypoint).
+ * Ratio mode (crop_ratio > 0, crop_height = crop_width = 0): size = ceil(max(x span, y span) * crop_ratio), made even, h = w = size.
+ * Fixed mode (crop_height, crop_width > 0, crop_ratio = 0): h = crop_height + crop_height % 2, w likewise.
+ * Corner = trunc(centroid - [h / 2, w / 2]) toward zero - (sic) x moves by half the HEIGHT, as in the reference, so box files interchange.
+ * Deviation: a frame with a non-finite anchor coordinate or a size of 0 gets [0, 0, 0, 0] (the reference crashes later on such a frame). */
+int lp_bbox_from_keypoints(const float* keypoints, int N, int K, const int* anchors, int n_anchors, double crop_ratio, int crop_height,
+                           int crop_width, int* bbox, lp_stream_t stream);
+/* DataFrame.rolling(window, center=True, min_periods=1).median().round(0).astype(int) per column (utils/cropzoom.py:391-392): frame i sees
+ * frames [i - window / 2, i + (window - 1) / 2] cut to [0, N); an even count gives the mean of the two middle values, rounded half to even.
+ * window > LP_BBOX_SMOOTH_MAX_WINDOW: LP_ERR_UNSUPPORTED.  bbox_out must not alias bbox_in. */
+int lp_bbox_smooth(const int* bbox_in, int N, int window, int* bbox_out, lp_stream_t stream);
+/* src u8 (S, Hs, Ws, 3) with byte strides, bbox (S, 4) int32 [x, y, h, w] ON THE DEVICE -> dst fp32 (S, 3, H, W) = (v / 255 - mean) / std.
+ * Frame s is the virtual h_s x w_s image whose pixel (i, j) is src[s][y_s + i][x_s + j] inside the frame and 0 outside it (zero padding);
+ * it is resampled to (H, W) by lp_frames_resize's rule (triangle filter of radius max(1, scale) per axis, `border` applied at the edge of
+ * the virtual image) with a scale of its own.  The result is bit-identical to lp_frames_resize of the materialised crop.  A box with
+ * h <= 0 or w <= 0 (or a side above 65536) gives the normalised black frame. */
+int lp_frames_crop_resize(const void* src_u8, int S, int Hs, int Ws, long long frame_stride, int row_stride, const int* bbox, int H, int W,
+                          int border, const lp_frame_norm* norm, float* dst, lp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Labeled-frame augmentation (csrc/labelaug.hip): the imgaug "dlc" presets of data/augmentations.py:122-238, restated from imgaug's

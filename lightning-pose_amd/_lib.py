@@ -72,7 +72,7 @@ AUG_LOCAL_BLUR_COARSE, AUG_LOCAL_EMBOSS = 0, 1
 AUG_ELASTIC_MAX_RADIUS = 20
 TF_NONE, TF_SINGLE, TF_PER_FRAME, TF_PER_VIEW = 0, 1, 2, 3
 
-ABI_VERSION = 150   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
+ABI_VERSION = 151   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -184,6 +184,9 @@ PROTOTYPES = {
     "lp_frames_resize": (_I, [_P, _I, _I, _I, C.c_longlong, _I, _I, _I, _I, C.POINTER(FrameNorm), _P, _P]),
     "lp_frames_resize_cubic": (_I, [_P, _I, _I, _I, C.c_longlong, _I, _I, _I, _I, C.POINTER(FrameNorm), _P, _P]),
     "lp_frames_augment": (_I, [_P, _I, _I, _I, C.POINTER(FrameAugment), C.POINTER(FrameNorm), _P, _P]),
+    "lp_bbox_from_keypoints": (_I, [_P, _I, _I, C.POINTER(C.c_int), _I, C.c_double, _I, _I, _P, _P]),
+    "lp_bbox_smooth": (_I, [_P, _I, _I, _P, _P]),
+    "lp_frames_crop_resize": (_I, [_P, _I, _I, _I, C.c_longlong, _I, _P, _I, _I, _I, C.POINTER(FrameNorm), _P, _P]),
     "lp_labeled_keypoints": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "lp_labelaug_geom": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "lp_labelaug_local": (_I, [_P, _I, _I, _I, _P, _I, _P, C.c_ulonglong, _P, _P]),

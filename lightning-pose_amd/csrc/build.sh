@@ -5,7 +5,7 @@
 set -euo pipefail
 cd "$(dirname "$0")"
 ROCM=${ROCM_PATH:-/opt/rocm}
-SRCS=(api.hip decode.hip heatmap.hip kploss.hip cameras.hip conv.hip bn.hip optim.hip vit.hip rope.hip attn.hip frames.hip labelaug.hip patchmask.hip mv3d.hip fp32.hip vit_f32.hip)
+SRCS=(api.hip decode.hip heatmap.hip kploss.hip cameras.hip conv.hip bn.hip optim.hip vit.hip rope.hip attn.hip frames.hip cropzoom.hip labelaug.hip patchmask.hip mv3d.hip fp32.hip vit_f32.hip)
 mode=${1:-hip}
 if [ "$mode" = emu ]; then
   out=../../tests/hipemu
@@ -15,7 +15,7 @@ if [ "$mode" = emu ]; then
   for s in "${SRCS[@]}"; do
     [ -f "$s" ] || continue
     o="$out/obj/${s%.hip}.o"
-    if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ lp_common.h -nt "$o" ] || { { [ "$s" = cameras.hip ] || [ "$s" = mv3d.hip ]; } && [ cam_common.h -nt "$o" ]; } || { { [ "$s" = vit.hip ] || [ "$s" = vit_f32.hip ]; } && [ vit_mv.h -nt "$o" ]; } || { { [ "$s" = frames.hip ] || [ "$s" = labelaug.hip ] || [ "$s" = patchmask.hip ]; } && [ frames_common.h -nt "$o" ]; } || { [ "$s" = conv.hip ] && { [ conv_pipe.h -nt "$o" ] || [ conv_res2d.h -nt "$o" ] || [ conv_stem_wgrad.h -nt "$o" ] || [ conv_wgrad_nb.h -nt "$o" ]; }; } || [ ../../include/lp_hip.h -nt "$o" ] || [ "$out/hip/hip_runtime.h" -nt "$o" ]; then
+    if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ lp_common.h -nt "$o" ] || { { [ "$s" = cameras.hip ] || [ "$s" = mv3d.hip ]; } && [ cam_common.h -nt "$o" ]; } || { { [ "$s" = vit.hip ] || [ "$s" = vit_f32.hip ]; } && [ vit_mv.h -nt "$o" ]; } || { { [ "$s" = frames.hip ] || [ "$s" = cropzoom.hip ] || [ "$s" = labelaug.hip ] || [ "$s" = patchmask.hip ]; } && [ frames_common.h -nt "$o" ]; } || { [ "$s" = conv.hip ] && { [ conv_pipe.h -nt "$o" ] || [ conv_res2d.h -nt "$o" ] || [ conv_stem_wgrad.h -nt "$o" ] || [ conv_wgrad_nb.h -nt "$o" ]; }; } || [ ../../include/lp_hip.h -nt "$o" ] || [ "$out/hip/hip_runtime.h" -nt "$o" ]; then
       "$ROCM/lib/llvm/bin/clang++" -x c++ -std=c++17 -O2 -fPIC -Wno-psabi -Wno-unused-value -I"$out" -c "$s" -o "$o" &
     fi
     objs+=("$o")
@@ -33,7 +33,7 @@ else
   for s in "${SRCS[@]}"; do
     [ -f "$s" ] || continue
     o="$od/${s%.hip}.o"
-    if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ lp_common.h -nt "$o" ] || { { [ "$s" = cameras.hip ] || [ "$s" = mv3d.hip ]; } && [ cam_common.h -nt "$o" ]; } || { { [ "$s" = vit.hip ] || [ "$s" = vit_f32.hip ]; } && [ vit_mv.h -nt "$o" ]; } || { { [ "$s" = frames.hip ] || [ "$s" = labelaug.hip ] || [ "$s" = patchmask.hip ]; } && [ frames_common.h -nt "$o" ]; } || { [ "$s" = conv.hip ] && { [ conv_pipe.h -nt "$o" ] || [ conv_res2d.h -nt "$o" ] || [ conv_stem_wgrad.h -nt "$o" ] || [ conv_wgrad_nb.h -nt "$o" ]; }; } || [ ../../include/lp_hip.h -nt "$o" ]; then
+    if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ lp_common.h -nt "$o" ] || { { [ "$s" = cameras.hip ] || [ "$s" = mv3d.hip ]; } && [ cam_common.h -nt "$o" ]; } || { { [ "$s" = vit.hip ] || [ "$s" = vit_f32.hip ]; } && [ vit_mv.h -nt "$o" ]; } || { { [ "$s" = frames.hip ] || [ "$s" = cropzoom.hip ] || [ "$s" = labelaug.hip ] || [ "$s" = patchmask.hip ]; } && [ frames_common.h -nt "$o" ]; } || { [ "$s" = conv.hip ] && { [ conv_pipe.h -nt "$o" ] || [ conv_res2d.h -nt "$o" ] || [ conv_stem_wgrad.h -nt "$o" ] || [ conv_wgrad_nb.h -nt "$o" ]; }; } || [ ../../include/lp_hip.h -nt "$o" ]; then
       "$ROCM/bin/hipcc" --offload-arch=gfx950 -O3 -std=c++17 -fPIC ${LP_BUILD_FLAGS:-} -c "$s" -o "$o" &
     fi
     objs+=("$o")

@@ -17,10 +17,6 @@
 
 namespace lp {
 
-struct NormSpec {
-    float mean[3], inv_std[3];
-};
-
 // ---- antialiased linear resize (triangle filter whose radius grows with the down-scale factor) -------------------------
 struct ResizeSpec {
     int Hs, Ws, H, W;
@@ -257,15 +253,6 @@ __global__ __launch_bounds__(256) void labeled_keypoints_kernel(const float* __r
 }  // namespace lp
 
 // ------------------------------------------------------------------------------------------------------- C ABI
-static bool norm_spec(const lp_frame_norm* n, lp::NormSpec& out) {
-    for (int c = 0; c < 3; ++c) {
-        if (!(n->std[c] > 0.f)) return false;
-        out.mean[c] = n->mean[c];
-        out.inv_std[c] = 1.f / n->std[c];
-    }
-    return true;
-}
-
 extern "C" int lp_frames_resize(const void* src_u8, int S, int Hs, int Ws, long long frame_stride, int row_stride, int H, int W, int border,
                                 const lp_frame_norm* finish_norm, float* dst, lp_stream_t stream) {
     using namespace lp;

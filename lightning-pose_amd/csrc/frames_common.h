@@ -1,11 +1,15 @@
-// Helpers shared by the batch-producer kernels (frames.hip, labelaug.hip): index clamping, the Keys bicubic taps of OpenCV's
-// INTER_CUBIC, and the counter-based Philox4x32-10 generator.
+// Helpers shared by the batch-producer kernels (frames.hip, cropzoom.hip, labelaug.hip): index clamping, the Keys bicubic taps of
+// OpenCV's INTER_CUBIC, the normalisation constants and the counter-based Philox4x32-10 generator.
 #pragma once
 #include "lp_common.h"
 
 namespace lp {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+struct NormSpec {
+    float mean[3], inv_std[3];
+};
 
 // Keys kernel with A = -0.75 on half-pixel centres: the four taps start at source pixel i0
 __device__ __forceinline__ void cubic_taps(float c, int& i0, float (&w)[4]) {
@@ -63,3 +67,12 @@ struct Philox {  // scalar members only: nothing here is indexed dynamically, so
 };
 
 }  // namespace lp
+
+static inline bool norm_spec(const lp_frame_norm* n, lp::NormSpec& out) {
+    for (int c = 0; c < 3; ++c) {
+        if (!(n->std[c] > 0.f)) return false;
+        out.mean[c] = n->mean[c];
+        out.inv_std[c] = 1.f / n->std[c];
+    }
+    return true;
+}

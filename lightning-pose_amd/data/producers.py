@@ -7,6 +7,10 @@
                          ranges (rotation U(-10, 10) deg, scale U(0.8, 1.2)^2, brightness / contrast U(0.75, 1.25), shot-noise
                          factor U(0, 10)), same outputs (the (2, 3) matrix the fused decode later undoes; the ``[-1]`` sentinel
                          when nothing geometric happened).  Video DECODE is not here: frames arrive as a uint8 tensor.
+``CropZoomFramePipeline`` the second pass of crop-zoom prediction (reference utils/cropzoom.py ``crop_video`` + the video loader's resize): every
+                         frame's own box, read from device memory, cropped (zero padding), resampled to the model's size and normalised
+                         in ONE launch (``lp_frames_crop_resize``) -> ``UnlabeledBatchDict`` whose per-frame ``bbox`` the fused decode
+                         maps the predictions back through.
 ``LabeledBatchProducer`` the per-batch work of ``HeatmapDataset.__getitem__`` (data/datasets.py:262-376, :496-550) moved to the
                          device: image resize + normalise, keypoint projection, optional flip with the left / right swap,
                          out-of-frame -> NaN, visibility synthesis, Gaussian targets (``lp_heatmap_gen``) -> ``HeatmapLabeledBatchDict``
@@ -119,6 +123,32 @@ class VideoFramePipeline:
         bbox = torch.cat([torch.tensor([0.0, 0.0, float(v[2][0]), float(v[2][1])], device=frames.device) for v in views]
                          ).repeat(frames.shape[0], 1)                           # (S, 4V)
         return MultiviewUnlabeledBatchDict(frames=frames, transforms=transforms, bbox=bbox, is_multiview=True)
+
+
+class CropZoomFramePipeline:
+    """Decoded frames + one box per frame -> the pose model's batch of crop-zoom prediction.  ``bbox`` is an integer (S, 4) tensor of rows
+    [x, y, h, w] (``ops.bbox_from_keypoints`` / ``ops.bbox_smooth`` leave it on the device; a host tensor is copied there).  No augmentation:
+    this is a prediction pipeline."""
+
+    def __init__(self, resize_dims: Sequence[int], normalization_mean: Sequence[float] = _IMAGENET_MEAN,
+                 normalization_std: Sequence[float] = _IMAGENET_STD, border: str = "clamp") -> None:
+        if resize_dims is None or len(resize_dims) != 2:
+            raise ValueError("resize_dims must be (height, width): the crops of different frames have different sizes")
+        if border not in ("clamp", "renorm"):
+            raise ValueError(f"border must be 'clamp' or 'renorm', got {border!r}")
+        self.resize_dims = (int(resize_dims[0]), int(resize_dims[1]))
+        self.mean, self.std = list(normalization_mean), list(normalization_std)
+        self.border = border
+
+    def __call__(self, frames_u8: torch.Tensor, bbox: torch.Tensor) -> UnlabeledBatchDict:
+        if not torch.is_tensor(frames_u8) or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+            raise ValueError(f"frames must be (S, H, W, 3) uint8, got {tuple(getattr(frames_u8, 'shape', ()))}")
+        if not torch.is_tensor(bbox) or bbox.is_floating_point() or tuple(bbox.shape) != (frames_u8.shape[0], 4):
+            raise ValueError(f"bbox must be an integer ({frames_u8.shape[0]}, 4) tensor of [x, y, h, w] rows")
+        boxes = bbox.to(device=frames_u8.device, dtype=torch.int32)
+        frames = ops.frames_crop_resize(frames_u8, boxes, self.resize_dims[0], self.resize_dims[1], self.mean, self.std, self.border)
+        return UnlabeledBatchDict(frames=frames, transforms=torch.tensor([-1.0]).to(frames.device), bbox=boxes.to(torch.float32),
+                                  is_multiview=False)
 
 
 class LabeledBatchProducer:

@@ -20,7 +20,7 @@ from ._lib import LpHipUnavailable, check
 
 __all__ = [
     "decode", "DecodeFrameMap", "generate_heatmaps", "heatmap_mse", "unimodal_mse", "temporal_loss", "pca_loss",
-    "rmse", "require_device", "frames_resize", "frames_augment", "labeled_keypoints", "patch_mask", "mv3d_plan", "mv3d_fill", "mv3d_finish",
+    "rmse", "require_device", "frames_resize", "frames_augment", "labeled_keypoints", "bbox_from_keypoints", "bbox_smooth", "frames_crop_resize", "patch_mask", "mv3d_plan", "mv3d_fill", "mv3d_finish",
 ]
 
 
@@ -787,6 +787,71 @@ def frames_resize(frames_u8: torch.Tensor, height: int, width: int, border: str 
     check(_lib.lib().lp_frames_resize(_p(frames_u8), s, hs, ws, frames_u8.stride(0), frames_u8.stride(1), int(height), int(width),
                                       _lib.BORDER_CLAMP if border == "clamp" else _lib.BORDER_RENORM,
                                       C.byref(norm) if finish else None, _p(out), _stream()), "lp_frames_resize")
+    return out
+
+
+BBOX_MAX_ANCHORS, BBOX_SMOOTH_MAX_WINDOW = 64, 255   # include/lp_hip.h: LP_BBOX_MAX_ANCHORS, LP_BBOX_SMOOTH_MAX_WINDOW
+
+
+def bbox_from_keypoints(keypoints: torch.Tensor, anchors: Sequence[int] = (), crop_ratio: float | None = None, crop_height: int | None = None,
+                        crop_width: int | None = None) -> torch.Tensor:
+    """(N, K, 2) or (N, 2K) fp32 device keypoints in frame px -> (N, 4) int32 boxes [x, y, h, w] on the device: the reference's
+    ``_compute_bbox_df`` (utils/cropzoom.py:65-143) in double precision, one launch, nothing read back.  ``anchors``: keypoint indices the
+    box is built from (empty: all).  Exactly one of ``crop_ratio`` and the pair (``crop_height``, ``crop_width``); frames with a non-finite
+    anchor or an empty box get [0, 0, 0, 0]."""
+    require_device(keypoints)
+    fixed = crop_height is not None and crop_width is not None
+    if fixed and crop_ratio is not None:
+        raise ValueError("provide either crop_ratio or (crop_height, crop_width), not both.")
+    if not fixed and crop_ratio is None:
+        raise ValueError("one of crop_ratio or (crop_height, crop_width) must be provided.")
+    if keypoints.dim() not in (2, 3) or (keypoints.dim() == 3 and keypoints.shape[-1] != 2) or keypoints.shape[-1] % 2 or keypoints.shape[0] == 0:
+        raise ValueError(f"keypoints must be (N, K, 2) or (N, 2K), got {tuple(keypoints.shape)}")
+    kp = _f32c(keypoints)
+    n, k = int(kp.shape[0]), int(kp.numel() // (2 * kp.shape[0]))
+    idx = [int(a) for a in anchors]
+    if any(a < 0 or a >= k for a in idx):
+        raise ValueError(f"anchor indices must lie in [0, {k}), got {idx}")
+    out = torch.empty(n, 4, device=kp.device, dtype=torch.int32)
+    arr = (C.c_int * max(1, len(idx)))(*idx)
+    check(_lib.lib().lp_bbox_from_keypoints(_p(kp), n, k, arr, len(idx), 0.0 if fixed else float(crop_ratio), int(crop_height) if fixed else 0,
+                                            int(crop_width) if fixed else 0, _p(out), _stream()), "lp_bbox_from_keypoints")
+    return out
+
+
+def bbox_smooth(bbox: torch.Tensor, window: int) -> torch.Tensor:
+    """(N, 4) int32 device boxes -> their centred rolling median (pandas ``rolling(window, center=True, min_periods=1).median().round(0)``,
+    utils/cropzoom.py:391-392), (N, 4) int32.  ``window`` above ``BBOX_SMOOTH_MAX_WINDOW`` is refused (NotImplementedError)."""
+    require_device(bbox)
+    if bbox.dtype != torch.int32 or bbox.dim() != 2 or bbox.shape[1] != 4 or bbox.shape[0] == 0:
+        raise ValueError(f"bbox must be int32 (N, 4), got {bbox.dtype} {tuple(bbox.shape)}")
+    if int(window) < 1:
+        raise ValueError(f"window must be at least 1, got {window}")
+    bb = bbox.contiguous()
+    out = torch.empty_like(bb)
+    check(_lib.lib().lp_bbox_smooth(_p(bb), int(bb.shape[0]), int(window), _p(out), _stream()), "lp_bbox_smooth")
+    return out
+
+
+def frames_crop_resize(frames_u8: torch.Tensor, bbox: torch.Tensor, height: int, width: int, mean, std, border: str = "clamp") -> torch.Tensor:
+    """(S, Hs, Ws, 3) uint8 device frames + (S, 4) int32 device boxes [x, y, h, w] -> fp32 (S, 3, height, width) normalised planes of each
+    frame's own box, in one launch: bit-identical to ``frames_resize(crop, height, width, border, mean, std)`` of the zero-padded crop."""
+    require_device(frames_u8, bbox)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+        raise ValueError(f"frames must be uint8 (S, H, W, 3), got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    if border not in ("clamp", "renorm"):
+        raise ValueError(f"border must be 'clamp' or 'renorm', got {border!r}")
+    if bbox.dtype != torch.int32 or tuple(bbox.shape) != (frames_u8.shape[0], 4):
+        raise ValueError(f"bbox must be int32 ({frames_u8.shape[0]}, 4), got {bbox.dtype} {tuple(bbox.shape)}")
+    if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3:
+        frames_u8 = frames_u8.contiguous()
+    s, hs, ws, _ = frames_u8.shape
+    bb = bbox.contiguous()
+    out = torch.empty((s, 3, int(height), int(width)), device=frames_u8.device, dtype=torch.float32)
+    norm = _frame_norm(mean, std)
+    check(_lib.lib().lp_frames_crop_resize(_p(frames_u8), s, hs, ws, frames_u8.stride(0), frames_u8.stride(1), _p(bb), int(height), int(width),
+                                           _lib.BORDER_CLAMP if border == "clamp" else _lib.BORDER_RENORM, C.byref(norm), _p(out), _stream()),
+          "lp_frames_crop_resize")
     return out
 
 

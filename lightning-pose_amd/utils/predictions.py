@@ -6,6 +6,9 @@ Mirror of ``lightning_pose/utils/predictions.py`` for the part that sits directl
 column layout and error behaviour; the arithmetic (trunk, head, fused decode incl. the bounding-box map) is the HIP
 path behind ``HeatmapTracker.predict_step`` - nothing here computes keypoints on the host.
 
+``predict_video_cropzoom`` is the reference's two-stage workflow (``litpose predict`` -> ``create_bbox`` -> ``smooth_bbox`` -> ``crop`` ->
+``predict`` with ``bbox_file``; utils/cropzoom.py) in one call that never leaves the device between the two models.
+
 Not mirrored (outside the hot path): video readers (DALI / pynvvc / OpenCV), labeled-video rendering, metric files.
 ``frame_count`` therefore takes the number of frames from the caller (``frame_count=...``) or from a reader-provided
 ``count_frames`` callable instead of opening the video with OpenCV.
@@ -222,4 +225,82 @@ def predict_video(video_file: str | list[str], model: Any, predict_loader: Itera
                 d.to_csv(f)
         else:
             df.to_csv(output_pred_file)
+    return df
+
+
+def _resize_dims(cfg: Any) -> tuple[int, int]:
+    dims = _get(_get(cfg, "data"), "image_resize_dims", None)
+    if dims is None:
+        raise ValueError("must include `image_resize_dims` (height, width) field in cfg.data")
+    return int(_get(dims, "height")), int(_get(dims, "width"))
+
+
+def predict_video_cropzoom(video_file: str, detector: Any, pose_model: Any, videos: Any, detector_cfg: Any, *, cfg_detector: Any = None,
+                           cfg_pose: Any = None, sequence_length: int = 16, smooth_window: int | None = None,
+                           output_pred_file: str | None = None, output_bbox_file: str | None = None,
+                           output_detector_pred_file: str | None = None, resident_bytes: int = 4 << 30, border: str = "clamp"):
+    """Two-stage prediction of one decoded video (``videos``: a uint8 array / tensor (N, H, W, 3)): the detector on whole frames -> one box
+    per frame from its keypoints (``detector_cfg``: ``anchor_keypoints`` and ``crop_ratio`` or ``crop_height`` / ``crop_width``, as
+    ``utils.cropzoom.generate_bbox``) -> optionally their rolling median over ``smooth_window`` frames -> the pose model on every frame's own
+    crop -> the pose model's table in ORIGINAL-frame coordinates (``predict_step`` maps through the per-frame ``bbox``).
+
+    Keypoints and boxes stay on the device from the detector's decode to the crop kernel; nothing is read back before the tables are made.
+    A video of at most ``resident_bytes`` keeps its device windows from the first pass for the second, so it crosses PCIe once.
+    Optional files, in the reference's formats: the detector's table, the (smoothed) box table ``x, y, h, w`` indexed by frame, the pose table.
+    Returns the pose table.  Single-view trackers only."""
+    from .. import ops
+    from ..data.producers import CropZoomFramePipeline, FrameWindowSource, VideoFramePipeline
+    from .cropzoom import anchor_indices, check_bbox_mode
+
+    if not isinstance(video_file, str):
+        raise NotImplementedError("crop-zoom prediction is single-view: pass one video file name")
+    det, pose = getattr(detector, "model", detector), getattr(pose_model, "model", pose_model)
+    cfg_det = cfg_detector if cfg_detector is not None else detector.config.cfg
+    cfg_pos = cfg_pose if cfg_pose is not None else pose_model.config.cfg
+    crop_ratio, crop_height, crop_width = (_get(detector_cfg, k) for k in ("crop_ratio", "crop_height", "crop_width"))
+    check_bbox_mode(crop_ratio, crop_height, crop_width)
+    det_names = list(_get(_get(cfg_det, "data"), "keypoint_names"))
+    anchors = anchor_indices(det_names, list(_get(detector_cfg, "anchor_keypoints", None) or []))
+    if smooth_window is not None and not 1 <= int(smooth_window) <= ops.BBOX_SMOOTH_MAX_WINDOW:
+        raise ValueError(f"smooth_window must lie in [1, {ops.BBOX_SMOOTH_MAX_WINDOW}], got {smooth_window}")
+
+    device = next(det.parameters()).device
+    source = FrameWindowSource(videos, sequence_length=sequence_length, device=device)
+    if len(source.videos) != 1:
+        raise NotImplementedError("crop-zoom prediction takes one video")
+    n_frames, video = source.frame_count, source.videos[0]
+    frame_bytes = int(np.prod(video.shape[1:]))
+    resident = len(source) * source.sequence_length * frame_bytes <= int(resident_bytes)
+    kept: list[torch.Tensor] = []
+
+    def first_pass():
+        pipe = VideoFramePipeline(_resize_dims(cfg_det), border=border)
+        for window in source:
+            if resident:
+                kept.append(window)
+            yield pipe(window)
+
+    handler = PredictionHandler(cfg=cfg_det, video_file=video_file, frame_count=n_frames)
+    det_preds = predict_batches(det, first_pass())
+    keypoints = torch.vstack([p[0] for p in det_preds])[:n_frames]     # the padded tail goes BEFORE the boxes are smoothed
+    boxes = ops.bbox_from_keypoints(keypoints, anchors, crop_ratio, crop_height, crop_width)
+    if smooth_window is not None:
+        boxes = ops.bbox_smooth(boxes, int(smooth_window))
+    pad = len(source) * source.sequence_length - n_frames
+    padded = boxes if pad == 0 else torch.cat([boxes, torch.zeros(pad, 4, dtype=boxes.dtype, device=boxes.device)])   # zero frames: no box
+
+    def second_pass():
+        pipe = CropZoomFramePipeline(_resize_dims(cfg_pos), border=border)
+        for i, window in enumerate(kept if resident else source):
+            yield pipe(window, padded[i * source.sequence_length:(i + 1) * source.sequence_length])
+
+    pose_preds = predict_batches(pose, second_pass())
+    kept.clear()
+    df = PredictionHandler(cfg=cfg_pos, video_file=video_file, frame_count=n_frames)(preds=[(p[0], p[1]) for p in pose_preds])
+    for path, table in ((output_detector_pred_file, lambda: handler(preds=[(p[0], p[1]) for p in det_preds])),
+                        (output_bbox_file, lambda: pd.DataFrame(boxes.cpu().numpy().astype(np.int64), columns=pd.Index(["x", "y", "h", "w"]))),
+                        (output_pred_file, lambda: df)):
+        if path is not None:
+            os.makedirs(os.path.dirname(str(path)) or ".", exist_ok=True)
+            table().to_csv(path)
     return df

@@ -25,7 +25,9 @@ HOT = ("lp::conv_pipe_kernel", "lp::conv_spec_kernel", "lp::conv_wgrad_pipe_kern
        # the DINOv2 step's LayerNorm walks: four per-lane accumulator arrays at NP = 6 (ViT-B) must stay in registers
        "lp::layernorm_ls_fwd_kernel", "lp::layernorm_ls_bwd_kernel",
        # the DINOv3 step: the rotation of q / k (24 launches per step) and the token assembly with registers
-       "lp::rope_kernel", "lp::vit_reg_tokens_fwd_kernel", "lp::vit_reg_tokens_bwd_kernel")
+       "lp::rope_kernel", "lp::vit_reg_tokens_fwd_kernel", "lp::vit_reg_tokens_bwd_kernel",
+       # crop-zoom prediction: the per-frame crop + resize (one launch per window of the second pass) and the two box kernels around it
+       "lp::frames_crop_resize_kernel", "lp::bbox_from_keypoints_kernel", "lp::bbox_smooth_kernel")
 # decode_bwd_kernel<R, TY, NE = 64, ...> is the catch-all instantiation for maps larger than any BASELINE config selects (ne > 18 elements per
 # thread: heat-maps above 96 x 96 at 512 threads); it keeps its element array in scratch by design
 ALLOWED_SCRATCH = (
