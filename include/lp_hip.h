@@ -54,8 +54,9 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * 146 = patch masking (lp_patch_mask_f32), 147 = LayerScale inside the LayerNorm walks (lp_layernorm_ls_*, the DINOv2 backbones),
  * 148 = the multi-view labeled batch with its 3-D augmentation (lp_mv3d_*), 149 = lp_conv_last_resident,
  * 150 = the DINOv3 backbones: lp_rope_*, lp_vit_reg_tokens_*, the prefix-dropping lp_layernorm_ls_*_px (and their fp32 forms),
- * 151 = crop-zoom prediction: lp_bbox_from_keypoints, lp_bbox_smooth, lp_frames_crop_resize. */
-#define LP_HIP_ABI_VERSION 151
+ * 151 = crop-zoom prediction: lp_bbox_from_keypoints, lp_bbox_smooth, lp_frames_crop_resize,
+ * 152 = prediction metrics: lp_kp_metrics. */
+#define LP_HIP_ABI_VERSION 152
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -188,6 +189,38 @@ int lp_rmse_fwd(const float* kp_targ, const float* kp_pred, int n_points, float*
  * n <= 8 DEVICE scalars; w, a: host arrays.  _bwd: gx[i] = w[i] * (g_weighted[i] + a[i] * g_total[0]); either gradient may be NULL. */
 int lp_loss_combine(const float* const* x, const float* w, const float* a, int n, float* weighted, float* total, lp_stream_t stream);
 int lp_loss_combine_bwd(const float* w, const float* a, int n, const float* g_weighted, const float* g_total, float* gx, lp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Prediction metrics (csrc/metrics.hip; reference metrics.py:47-184, losses/losses.py:651-672, utils/pca.py:266-309): up to four (T, K)
+ * fp32 tables from a device-resident prediction table in ONE launch on the caller's stream; nothing is read back.
+ *   pred (T, K, 2); labels (T, K, 2) or NULL.  An output pointer that is NULL is a table that is not wanted (at least one must be given).
+ *   pixel_error[t,k]   = ||labels[t,k] - pred[t,k]||                      (needs labels; NaN where a coordinate of either is NaN)
+ *   temporal_norm[t,k] = ||pred[t,k] - pred[t-1,k]|| for t >= 1, NaN for t = 0   (no epsilon, no confidence mask, no relu)
+ *   pca_singleview[t,k]: frame t is one sample over the `points` keypoints of the index row; keypoint index[p] gets the Euclidean norm of
+ *       its 2-D residual (x - mean) - V^T V (x - mean), every other column NaN.  rows must be 1.
+ *   pca_multiview[t,k]: sample (t, j) gathers keypoints index[j][0 .. points) (one per view); their residual norms go to those columns,
+ *       every other column NaN.
+ *   A NaN coordinate in a PCA sample makes every entry of that sample NaN (the reference's matmul); +-Inf is not specified.  A column that
+ *   an index table lists more than once takes the value of its LAST entry (numpy's fancy assignment).
+ * lp_pca_spec: index (rows, points) int32 as KeypointPCA.index_table builds it for lp_pca_fwd_bwd, on the DEVICE, and index_host, the same
+ * table in HOST memory: it is checked before the launch.  mean (2 points), kept_eigenvectors (ncomp, 2 points): device fp32.
+ * Every element of every requested table is written exactly once (the NaN fills too): no memset beforehand, no atomics, no workspace, and
+ * the same bits from run to run and for any launch geometry.
+ * LP_ERR_ARGUMENT (nothing launched): a null pred, T or K < 1, no output, pixel_error without labels, a PCA output without its spec,
+ *   points > 64, ncomp > 2 points, ncomp < 0, an index_host entry outside [0, K), rows != 1 for the single-view spec, rows points > 2^24.
+ * LP_ERR_UNSUPPORTED (nothing launched): 2 T K >= 2^31 elements, or eigenvectors + owner maps ((ncomp 2 points + K) words per requested
+ *   PCA table) beyond the 160 KB of one workgroup's LDS.
+ * ------------------------------------------------------------------------------------------------------ */
+typedef struct lp_pca_spec {
+    const int* index;               /* device (rows, points) */
+    const int* index_host;          /* host copy of the same table */
+    int rows, points;
+    const float* mean;              /* device (2 points) */
+    const float* kept_eigenvectors; /* device (ncomp, 2 points) */
+    int ncomp;
+} lp_pca_spec;
+int lp_kp_metrics(const float* pred, const float* labels, int T, int K, const lp_pca_spec* singleview, const lp_pca_spec* multiview,
+                  float* pixel_error, float* temporal_norm, float* pca_singleview, float* pca_multiview, lp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Backbone / head contractions on the matrix cores (bf16 NHWC activations, fp32 accumulate).

@@ -46,6 +46,11 @@ class FrameAugment(C.Structure):
                 ("contrast_center", C.c_float), ("shot_factor", C.c_float), ("seed", C.c_ulonglong)]
 
 
+class PcaSpec(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("index_host", C.c_void_p), ("rows", C.c_int), ("points", C.c_int), ("mean", C.c_void_p),
+                ("kept_eigenvectors", C.c_void_p), ("ncomp", C.c_int)]
+
+
 class GemmBatch(C.Structure):
     _fields_ = [("nb", C.c_int), ("nh", C.c_int)] + [(n, C.c_longlong) for n in ("a_b", "a_h", "b_b", "b_h", "c_b", "c_h")]
 
@@ -72,7 +77,7 @@ AUG_LOCAL_BLUR_COARSE, AUG_LOCAL_EMBOSS = 0, 1
 AUG_ELASTIC_MAX_RADIUS = 20
 TF_NONE, TF_SINGLE, TF_PER_FRAME, TF_PER_VIEW = 0, 1, 2, 3
 
-ABI_VERSION = 151   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
+ABI_VERSION = 152   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -105,6 +110,7 @@ PROTOTYPES = {
     "lp_rmse_fwd": (_I, [_P, _P, _I, _P, _P]),
     "lp_loss_combine": (_I, [_P, _P, _P, _I, _P, _P, _P]),
     "lp_loss_combine_bwd": (_I, [_P, _P, _I, _P, _P, _P, _P]),
+    "lp_kp_metrics": (_I, [_P, _P, _I, _I, C.POINTER(PcaSpec), C.POINTER(PcaSpec), _P, _P, _P, _P, _P]),
     "lp_conv_fwd": (_I, [_P, _P, C.POINTER(ConvGeom), _P, _P, _P, _I, _I, _P]),
     "lp_conv_dgrad": (_I, [_P, _P, C.POINTER(ConvGeom), _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "lp_conv_dgrad_bits": (_I, [_P, _P, C.POINTER(ConvGeom), _P, _P, _P, _I, _P]),

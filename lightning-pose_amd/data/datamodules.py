@@ -52,6 +52,17 @@ class BaseDataModule:
             yield self.dataset.batch(list(indices[lo:lo + batch_size]), hflip=torch.zeros(len(indices[lo:lo + batch_size]), dtype=torch.bool)
                                      if getattr(self.dataset, "imgaug_hflip", False) else None, **kw)
 
+    def pca_keypoints(self) -> torch.Tensor:
+        """(N_train, 2K) un-augmented keypoints of the training split, NaN where unlabeled: what ``KeypointPCA`` fits the pca_singleview /
+        pca_multiview losses and metrics on.  It is what the reference's ``DataExtractor(data_module, cond="train",
+        remove_augmentations=True)`` collects (data/extractor.py) - the ``keypoints`` of ``dataset.batch(idx, augment=False)`` for the
+        training indices, in their order - made from the label table and the image file headers alone: no image is decoded.
+
+        The reference's convention, kept here because changing it would change every number the reference reports: the fit is in
+        MODEL-pixel coordinates (labels scaled to the network's input size), while the PCA METRICS are then applied to predictions in
+        FRAME pixels (metrics.py:274-325).  The two agree only when frames are stored at the model's input size."""
+        return self.dataset.unaugmented_keypoints(list(self.train_dataset.indices))
+
     def _rank_world(self) -> tuple[int, int]:
         import torch.distributed as dist
 

@@ -31,6 +31,7 @@ import torch
 
 from pathlib import Path
 
+from .. import ops
 from .augmentations import LabeledAugmentation
 from .cameras import CameraGroup
 from .datatypes import HeatmapLabeledBatchDict, MultiviewHeatmapLabeledBatchDict
@@ -151,6 +152,28 @@ class HeatmapDataset:
         if len({f.shape for f in frames}) != 1:
             raise ValueError(f"images of one batch must share a size, got {sorted({f.shape for f in frames})}")
         return torch.from_numpy(np.stack(frames))
+
+    def image_sizes(self, indices: Sequence[int]) -> torch.Tensor:
+        """(B, 2) float32 stored (height, width) of these examples' images, read from the file headers: no image is decoded."""
+        from PIL import Image
+
+        sizes = []
+        for i in indices:
+            with Image.open(os.path.join(self.root_directory, self.image_names[int(i)])) as im:
+                w, h = im.size
+            sizes.append([float(h), float(w)])
+        return torch.tensor(sizes, dtype=torch.float32).reshape(-1, 2)
+
+    def unaugmented_keypoints(self, indices: Sequence[int]) -> torch.Tensor:
+        """(B, 2K) model-px keypoints of these examples, NaN where unlabeled or out of frame: the ``keypoints`` of ``batch(indices,
+        hflip=None-or-zeros, augment=False)`` bit for bit (the same ``lp_labeled_keypoints`` launch), without loading an image."""
+        idx = torch.as_tensor(list(indices), dtype=torch.long)
+        if len(idx) == 0:
+            return torch.empty(0, self.num_targets, device=self.device)
+        kp_model, _ = ops.labeled_keypoints(self.keypoints[idx].to(self.device), self.image_sizes(idx.tolist()).to(self.device),
+                                            self.height, self.width, swap=self.producer.swap, visibility=self.visibility[idx].to(self.device),
+                                            uniform_heatmaps=self.uniform_heatmaps)
+        return kp_model.reshape(len(idx), self.num_targets)
 
     def batch(self, indices: Sequence[int], hflip: torch.Tensor | None = None, augment: bool = True) -> HeatmapLabeledBatchDict:
         """The labeled batch of the step for these examples; ``hflip`` (B,) overrides the random flip decisions of ``imgaug_hflip``;
@@ -329,6 +352,11 @@ class MultiviewHeatmapDataset:
         if calib_file not in self._rigs:
             self._rigs[calib_file] = tuple(t[0] for t in self.cam_params_file_to_camgroup[calib_file].rig(1, device="cpu"))
         return self._rigs[calib_file]
+
+    def unaugmented_keypoints(self, indices: Sequence[int]) -> torch.Tensor:
+        """(B, 2 V K) model-px keypoints, the views side by side in ``view_names`` order: the ``keypoints`` of ``batch(indices,
+        augment=False)`` (every view takes ``HeatmapDataset``'s path there), without loading an image."""
+        return torch.cat([self.dataset[v].unaugmented_keypoints(indices) for v in self.view_names], dim=1)
 
     def batch(self, indices: Sequence[int], hflip: torch.Tensor | None = None, augment: bool = True,
               params: np.ndarray | None = None) -> MultiviewHeatmapLabeledBatchDict:

@@ -20,7 +20,7 @@ from ._lib import LpHipUnavailable, check
 
 __all__ = [
     "decode", "DecodeFrameMap", "generate_heatmaps", "heatmap_mse", "unimodal_mse", "temporal_loss", "pca_loss",
-    "rmse", "require_device", "frames_resize", "frames_augment", "labeled_keypoints", "bbox_from_keypoints", "bbox_smooth", "frames_crop_resize", "patch_mask", "mv3d_plan", "mv3d_fill", "mv3d_finish",
+    "rmse", "keypoint_metrics", "PcaMetricSpec", "require_device", "frames_resize", "frames_augment", "labeled_keypoints", "bbox_from_keypoints", "bbox_smooth", "frames_crop_resize", "patch_mask", "mv3d_plan", "mv3d_fill", "mv3d_finish",
 ]
 
 
@@ -543,6 +543,68 @@ def pca_loss(keypoints: torch.Tensor, index: torch.Tensor, mean: torch.Tensor, k
     check(_lib.lib().lp_pca_fwd_bwd(_p(kp), s, k, _p(index), rows, pts, _p(mean), _p(kept_eigenvectors),
                                     kept_eigenvectors.shape[0], float(epsilon), _p(loss), _p(grad), _stream()), "lp_pca_fwd_bwd")
     return _UnitGradFn.apply(keypoints, loss.reshape(()), grad)
+
+
+class PcaMetricSpec:
+    """One PCA table of ``keypoint_metrics``: the index table (rows, points) of ``KeypointPCA.index_table`` with the fitted mean and kept
+    eigenvectors on ``device``.  The index table is kept twice: on the device for the kernel, on the host for the check before the launch."""
+
+    def __init__(self, index, mean: torch.Tensor, kept_eigenvectors: torch.Tensor, device: torch.device | str) -> None:
+        index_host = np.ascontiguousarray(index.detach().cpu().numpy() if torch.is_tensor(index) else np.asarray(index)).astype(np.int32)
+        if index_host.ndim != 2 or index_host.size == 0:
+            raise ValueError(f"index must be a non-empty (rows, points) table, got shape {index_host.shape}")
+        self.index_host = index_host
+        self.rows, self.points = (int(n) for n in index_host.shape)
+        dev = torch.device(device)
+        self.index = torch.from_numpy(index_host).to(dev)
+        # raw pointers go to the kernel: dense row-major fp32 (as pca_loss)
+        self.mean = _f32c(torch.as_tensor(mean)).reshape(-1).to(dev)
+        self.kept_eigenvectors = _f32c(torch.as_tensor(kept_eigenvectors)).to(dev)
+        if self.mean.numel() != 2 * self.points or self.kept_eigenvectors.dim() != 2 or self.kept_eigenvectors.shape[1] != 2 * self.points:
+            raise ValueError(f"pca metric: mean {tuple(self.mean.shape)} / eigenvectors {tuple(self.kept_eigenvectors.shape)} do not span the "
+                             f"{2 * self.points} coordinates of a sample ({self.points} points)")
+        self.ncomp = int(self.kept_eigenvectors.shape[0])
+
+    @classmethod
+    def from_pca(cls, pca, num_keypoints: int, device: torch.device | str) -> "PcaMetricSpec":
+        """from a fitted ``utils.pca.KeypointPCA``"""
+        return cls(pca.index_table(num_keypoints), pca.parameters["mean"], pca.parameters["kept_eigenvectors"], device)
+
+    def struct(self) -> _lib.PcaSpec:
+        return _lib.PcaSpec(self.index.data_ptr(), self.index_host.ctypes.data, self.rows, self.points, self.mean.data_ptr(),
+                            self.kept_eigenvectors.data_ptr() if self.ncomp else None, self.ncomp)
+
+
+def keypoint_metrics(keypoints_pred: torch.Tensor, keypoints_true: torch.Tensor | None = None, pca_singleview: PcaMetricSpec | None = None,
+                     pca_multiview: PcaMetricSpec | None = None, *, temporal: bool = True) -> dict[str, torch.Tensor]:
+    """(T, K, 2) or (T, 2K) device predictions -> the requested (T, K) fp32 metric tables, on the device, from ONE launch of
+    ``lp_kp_metrics`` (reference metrics.py:47-184): ``"temporal_norm"`` (``temporal``), ``"pixel_error"`` (``keypoints_true`` given, same
+    shape), ``"pca_singleview_error"`` / ``"pca_multiview_error"`` (their spec given).  Nothing is read back."""
+    require_device(keypoints_pred, keypoints_true)
+    if keypoints_pred.dim() not in (2, 3) or (keypoints_pred.dim() == 3 and keypoints_pred.shape[-1] != 2) or keypoints_pred.shape[-1] % 2 \
+            or keypoints_pred.numel() == 0:
+        raise ValueError(f"keypoints_pred must be a non-empty (T, K, 2) or (T, 2K), got {tuple(keypoints_pred.shape)}")
+    pred = _f32c(keypoints_pred)
+    t, k = int(pred.shape[0]), int(pred.numel() // (2 * pred.shape[0]))
+    true = None
+    if keypoints_true is not None:
+        true = _f32c(keypoints_true)
+        if true.numel() != pred.numel() or true.shape[0] != t:
+            raise ValueError(f"keypoints_true {tuple(keypoints_true.shape)} and keypoints_pred {tuple(keypoints_pred.shape)} differ in size")
+    names = [n for n, wanted in (("pixel_error", true is not None), ("temporal_norm", temporal), ("pca_singleview_error", pca_singleview is not None),
+                                 ("pca_multiview_error", pca_multiview is not None)) if wanted]
+    if not names:
+        raise ValueError("keypoint_metrics: nothing to compute (no labels, temporal=False, no PCA spec)")
+    for spec in (pca_singleview, pca_multiview):
+        if spec is not None:
+            require_device(spec.index, spec.mean, spec.kept_eigenvectors)
+    out = {n: torch.empty(t, k, device=pred.device, dtype=torch.float32) for n in names}
+    sv = None if pca_singleview is None else pca_singleview.struct()
+    mv = None if pca_multiview is None else pca_multiview.struct()
+    check(_lib.lib().lp_kp_metrics(_p(pred), _p(true), t, k, None if sv is None else C.byref(sv), None if mv is None else C.byref(mv),
+                                   _p(out.get("pixel_error")), _p(out.get("temporal_norm")), _p(out.get("pca_singleview_error")),
+                                   _p(out.get("pca_multiview_error")), _stream()), "lp_kp_metrics")
+    return out
 
 
 def rmse(keypoints_targ: torch.Tensor, keypoints_pred: torch.Tensor) -> torch.Tensor:

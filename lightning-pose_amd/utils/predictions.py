@@ -9,7 +9,11 @@ path behind ``HeatmapTracker.predict_step`` - nothing here computes keypoints on
 ``predict_video_cropzoom`` is the reference's two-stage workflow (``litpose predict`` -> ``create_bbox`` -> ``smooth_bbox`` -> ``crop`` ->
 ``predict`` with ``bbox_file``; utils/cropzoom.py) in one call that never leaves the device between the two models.
 
-Not mirrored (outside the hot path): video readers (DALI / pynvvc / OpenCV), labeled-video rendering, metric files.
+With ``compute_metrics=True`` the three prediction calls also evaluate the table (reference: ``compute_metrics_single`` after every predict
+call of its API): the stacked predictions go through ``lp_kp_metrics`` while still on the device, the metric files are written next to the
+prediction file, and the call returns ``PredictionResult`` / ``MultiviewPredictionResult`` (data/datatypes.py).
+
+Not mirrored (outside the hot path): video readers (DALI / pynvvc / OpenCV), labeled-video rendering.
 ``frame_count`` therefore takes the number of frames from the caller (``frame_count=...``) or from a reader-provided
 ``count_frames`` callable instead of opening the video with OpenCV.
 """
@@ -170,9 +174,44 @@ def predict_batches(model: Any, batches: Iterable[dict], return_heatmaps: bool =
     return out
 
 
-def predict_dataset(model: Any, data_module: Any, preds_file: str | list[str], cfg: Any = None):
+def _labels_on_device(labels_file: Any, index: pd.Index, dataset: Any, device: torch.device) -> torch.Tensor:
+    """(N, K, 2) fp32 labels of a labeled table on ``device``: the label file read as ``compute_metrics_single`` reads it (x / y columns
+    only, an all-NaN first row restored, the index checked against the predictions'), or - no file given - the dataset's own parsed
+    labels.  Either way float64 file values narrowed to fp32 once, the cast ``compute_metrics_single`` applies."""
+    if labels_file is None:
+        assert list(dataset.image_names) == list(index)
+        return dataset.keypoints.to(device)
+    from ..metrics import fix_empty_first_row
+
+    labels_df = fix_empty_first_row(pd.read_csv(labels_file, header=[0, 1, 2], index_col=0))
+    assert labels_df.index.equals(index)
+    labels_df = labels_df.loc[:, labels_df.columns.get_level_values("coords").isin(["x", "y"])]
+    return torch.as_tensor(labels_df.to_numpy().reshape(labels_df.shape[0], -1, 2)).to(torch.float32).to(device)
+
+
+def _table_metrics(keypoints: torch.Tensor, labels: torch.Tensor | None, df: pd.DataFrame, cfg: Any, data_module: Any, preds_file: Any):
+    """``ComputeMetricsSingleResult`` of one single-view table from its DEVICE keypoints (T, 2K): what ``compute_metrics_single`` computes
+    from the written file, without the round trip through it.  Files are written only next to a prediction file."""
+    from .. import metrics
+
+    is_video = df.keys()[-1][0] != "set"
+    tables = metrics.metric_tables(keypoints, labels, cfg, data_module, is_video=is_video)
+    return metrics.metrics_result(tables, df.index, [c[1] for c in df.columns if c[2] == "x"], None if is_video else df.iloc[:, -1].to_numpy(),
+                                  preds_file)
+
+
+def _per_view(stacked: torch.Tensor, num_keypoints: int, view_idx: int) -> torch.Tensor:
+    return stacked[:, view_idx * num_keypoints * 2:(view_idx + 1) * num_keypoints * 2]
+
+
+def predict_dataset(model: Any, data_module: Any, preds_file: str | list[str], cfg: Any = None, *, compute_metrics: bool = False,
+                    labels_file: str | list[str] | None = None):
     """Predict every labeled frame and save the table(s) (reference :332-393).  ``model`` is the tracker itself or an object
-    with ``.model`` / ``.config.cfg`` like the reference's API wrapper."""
+    with ``.model`` / ``.config.cfg`` like the reference's API wrapper.
+
+    ``compute_metrics=True``: pixel error (and the PCA metrics the cfg / data module call for) from the device predictions, written next to
+    every prediction file; returns ``PredictionResult`` (``MultiviewPredictionResult``: each view evaluated as a single-view table, no PCA).
+    ``labels_file`` (one per view for a multi-view dataset): the label CSV(s) to compare with; default: the dataset's own labels."""
     module = getattr(model, "model", model)
     cfg_eff = cfg if cfg is not None else model.config.cfg
     preds = predict_batches(module, data_module.full_labeled_dataloader())
@@ -180,24 +219,44 @@ def predict_dataset(model: Any, data_module: Any, preds_file: str | list[str], c
     df = handler(preds=[(p[0], p[1]) for p in preds])
     if isinstance(df, dict):
         if isinstance(preds_file, str):
-            for view_name, d in df.items():
-                d.to_csv(preds_file.replace(".csv", f"_{view_name}.csv"))
+            files = [preds_file.replace(".csv", f"_{view_name}.csv") for view_name in df]
         else:
             assert list(df.keys()) == list(_get(_get(cfg_eff, "data"), "view_names"))
             if len(preds_file) != len(df):
                 raise ValueError("preds_file must have one entry per view")
-            for d, f in zip(df.values(), preds_file):
-                d.to_csv(f)
+            files = list(preds_file)
+        for d, f in zip(df.values(), files):
+            d.to_csv(f)
     else:
         assert isinstance(preds_file, str), "preds_file must be a str for single-view predictions"
         df.to_csv(preds_file)
-    return df
+    if not compute_metrics:
+        return df
+    from ..data.datatypes import MultiviewPredictionResult, PredictionResult
+
+    stacked = handler.unpack_preds(preds=[(p[0], p[1]) for p in preds])[0]
+    if isinstance(df, dict):
+        if labels_file is not None and (isinstance(labels_file, str) or len(labels_file) != len(df)):
+            raise ValueError("labels_file must have one entry per view")
+        k = len(handler.keypoint_names)
+        results = {}
+        for i, (view_name, d) in enumerate(df.items()):
+            labels = _labels_on_device(None if labels_file is None else labels_file[i], d.index, data_module.dataset.dataset[view_name], stacked.device)
+            results[view_name] = _table_metrics(_per_view(stacked, k, i), labels, d, cfg_eff, data_module, files[i])
+        return MultiviewPredictionResult(predictions=df, metrics=results)
+    labels = _labels_on_device(labels_file, df.index, data_module.dataset, stacked.device)
+    return PredictionResult(predictions=df, metrics=_table_metrics(stacked, labels, df, cfg_eff, data_module, preds_file))
 
 
 def predict_video(video_file: str | list[str], model: Any, predict_loader: Iterable[dict], output_pred_file: str | list[str] | None = None,
-                  *, cfg: Any = None, frame_count: int | None = None, count_frames: Callable[[str], int] | None = None):
+                  *, cfg: Any = None, frame_count: int | None = None, count_frames: Callable[[str], int] | None = None,
+                  compute_metrics: bool = False, data_module: Any = None):
     """Predict one video (or one video per view) from a loader of ``{"frames", "bbox", ...}`` batches and save the table(s)
-    (reference :416-548).  The loader is the caller's: building it from a file is the video producer's job (8f N1)."""
+    (reference :416-548).  The loader is the caller's: building it from a file is the video producer's job (8f N1).
+
+    ``compute_metrics=True``: the temporal norm (and, with ``data_module``, the PCA metrics its cfg calls for) of the device predictions
+    after the padded rows are dropped, written next to every prediction file; returns ``PredictionResult``, or
+    ``MultiviewPredictionResult`` keyed by view name (each view a single-view table)."""
     is_multiview = not isinstance(video_file, str)
     module = getattr(model, "model", model)
     cfg_eff = cfg if cfg is not None else model.config.cfg
@@ -225,7 +284,17 @@ def predict_video(video_file: str | list[str], model: Any, predict_loader: Itera
                 d.to_csv(f)
         else:
             df.to_csv(output_pred_file)
-    return df
+    if not compute_metrics:
+        return df
+    from ..data.datatypes import MultiviewPredictionResult, PredictionResult
+
+    stacked = handler.unpack_preds(preds=[(p[0], p[1]) for p in preds])[0]
+    if is_multiview:
+        k = len(handler.keypoint_names)
+        results = {v: _table_metrics(_per_view(stacked, k, i), None, d, cfg_eff, data_module, None if output_pred_file is None else output_pred_file[i])
+                   for i, (v, d) in enumerate(zip(view_names, df))}
+        return MultiviewPredictionResult(predictions=dict(zip(view_names, df)), metrics=results)
+    return PredictionResult(predictions=df, metrics=_table_metrics(stacked, None, df, cfg_eff, data_module, output_pred_file))
 
 
 def _resize_dims(cfg: Any) -> tuple[int, int]:
@@ -238,7 +307,8 @@ def _resize_dims(cfg: Any) -> tuple[int, int]:
 def predict_video_cropzoom(video_file: str, detector: Any, pose_model: Any, videos: Any, detector_cfg: Any, *, cfg_detector: Any = None,
                            cfg_pose: Any = None, sequence_length: int = 16, smooth_window: int | None = None,
                            output_pred_file: str | None = None, output_bbox_file: str | None = None,
-                           output_detector_pred_file: str | None = None, resident_bytes: int = 4 << 30, border: str = "clamp"):
+                           output_detector_pred_file: str | None = None, resident_bytes: int = 4 << 30, border: str = "clamp",
+                           compute_metrics: bool = False, data_module: Any = None):
     """Two-stage prediction of one decoded video (``videos``: a uint8 array / tensor (N, H, W, 3)): the detector on whole frames -> one box
     per frame from its keypoints (``detector_cfg``: ``anchor_keypoints`` and ``crop_ratio`` or ``crop_height`` / ``crop_width``, as
     ``utils.cropzoom.generate_bbox``) -> optionally their rolling median over ``smooth_window`` frames -> the pose model on every frame's own
@@ -247,7 +317,10 @@ def predict_video_cropzoom(video_file: str, detector: Any, pose_model: Any, vide
     Keypoints and boxes stay on the device from the detector's decode to the crop kernel; nothing is read back before the tables are made.
     A video of at most ``resident_bytes`` keeps its device windows from the first pass for the second, so it crosses PCIe once.
     Optional files, in the reference's formats: the detector's table, the (smoothed) box table ``x, y, h, w`` indexed by frame, the pose table.
-    Returns the pose table.  Single-view trackers only."""
+    Returns the pose table.  Single-view trackers only.
+
+    ``compute_metrics=True``: the pose table's temporal norm (and, with ``data_module``, the PCA metrics ``cfg_pose`` calls for) from the
+    device keypoints after the map back through the boxes, written next to ``output_pred_file``; returns ``PredictionResult``."""
     from .. import ops
     from ..data.producers import CropZoomFramePipeline, FrameWindowSource, VideoFramePipeline
     from .cropzoom import anchor_indices, check_bbox_mode
@@ -296,11 +369,17 @@ def predict_video_cropzoom(video_file: str, detector: Any, pose_model: Any, vide
 
     pose_preds = predict_batches(pose, second_pass())
     kept.clear()
-    df = PredictionHandler(cfg=cfg_pos, video_file=video_file, frame_count=n_frames)(preds=[(p[0], p[1]) for p in pose_preds])
+    pose_handler = PredictionHandler(cfg=cfg_pos, video_file=video_file, frame_count=n_frames)
+    df = pose_handler(preds=[(p[0], p[1]) for p in pose_preds])
     for path, table in ((output_detector_pred_file, lambda: handler(preds=[(p[0], p[1]) for p in det_preds])),
                         (output_bbox_file, lambda: pd.DataFrame(boxes.cpu().numpy().astype(np.int64), columns=pd.Index(["x", "y", "h", "w"]))),
                         (output_pred_file, lambda: df)):
         if path is not None:
             os.makedirs(os.path.dirname(str(path)) or ".", exist_ok=True)
             table().to_csv(path)
+    if compute_metrics:
+        from ..data.datatypes import PredictionResult
+
+        stacked = pose_handler.unpack_preds(preds=[(p[0], p[1]) for p in pose_preds])[0]
+        return PredictionResult(predictions=df, metrics=_table_metrics(stacked, None, df, cfg_pos, data_module, output_pred_file))
     return df
