@@ -626,7 +626,9 @@ int lp_small_matmul(const float* w, const float* x, int R, int Q, int D, int tra
  * lp_f32_layernorm_fwd differs there: without a delta it never writes x_out.) */
 int lp_layernorm_fwd(const float* x, const void* delta_bf16, float* x_out, const float* gamma, const float* beta, float eps, int M,
                      int D, int drop_T, void* y_bf16, float* mean, float* rstd, lp_stream_t stream);
-/* dx_acc += LayerNorm backward of dy (bf16, same row mapping as y);  dgamma_acc / dbeta_acc accumulate too */
+/* dx_acc += LayerNorm backward of dy (bf16, same row mapping as y);  dgamma_acc / dbeta_acc accumulate too.  A row that drop_T leaves
+ * without a dy takes dy = 0: its dx_acc stays bit for bit, and in the two forms below its dx_bf16 is the cast of that value and it is
+ * part of the column sums (as the LayerScale forms further down say of their own dropped rows). */
 int lp_layernorm_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma, int M, int D,
                      int drop_T, float* dx_acc, float* dgamma_acc, float* dbeta_acc, lp_stream_t stream);
 /* same, and the updated dx_acc is also written rounded to bf16 (what the next Linear layer's backward reads; the LayerNorms are

@@ -5,7 +5,8 @@ Everything here runs in torch float64 on the operands' device: im2col (F.unfold)
 (those may take reduced-precision paths).  Beside every result r the helpers return S = sum |a b| over the products behind it (the same
 matmul on |A| and |B|): the scale of the rounding error an fp32-accumulating kernel may make, whatever the signs.
 
-Used by tests/test_step_contractions_fp64.py and, from "fp32 validation kernels" down, by tests/test_fp32_validation_kernels.py.
+Used by tests/test_step_contractions_fp64.py, from "fp32 validation kernels" down by tests/test_fp32_validation_kernels.py, and from
+"bf16 ViT glue kernels" down by tests/test_vit_bf16_kernels.py.
 """
 
 from __future__ import annotations
@@ -271,3 +272,68 @@ def patchify(img: torch.Tensor, P: int) -> torch.Tensor:
     """(B, 3, H, W) -> (B gh gw, 3 P P), k = (c, ky, kx)"""
     B, _, H, W = img.shape
     return img.reshape(B, 3, H // P, P, W // P, P).permute(0, 2, 4, 1, 3, 5).reshape(B * (H // P) * (W // P), 3 * P * P)
+
+
+# ---------------------------------------------------------------------------------------------------------------- bf16 ViT glue kernels
+# bf16 operands and results travel as int16 tensors of bits (tests/test_vit_bf16_kernels.py); integer arithmetic, no torch.bfloat16 cast.
+def bf16_bits(x: torch.Tensor) -> torch.Tensor:
+    """float32 -> bf16 bit patterns (int16), round to nearest even; +-inf stay, a NaN becomes a quiet NaN, an fp32 denormal rounds like any
+    other value (to a bf16 denormal or to the smallest normal)"""
+    u = x.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    r = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+    r = torch.where((u & 0x7FFFFFFF) > 0x7F800000, (u >> 16) | 0x40, r)
+    return (((r & 0xFFFF) ^ 0x8000) - 0x8000).to(torch.int16)
+
+
+def bf16_f32(bits: torch.Tensor) -> torch.Tensor:
+    """int16 bf16 bit patterns -> the float32 values they stand for (exact)"""
+    return (bits.to(torch.int32) * 65536).view(torch.float32)
+
+
+def bf16_value(bits: torch.Tensor) -> torch.Tensor:
+    return bf16_f32(bits).to(F64)
+
+
+def bf16_trunc(r: torch.Tensor) -> torch.Tensor:
+    """the truncation mutant: the low 16 bits of r's fp32 image cleared (a bf16 store that chops instead of rounding), as float64"""
+    return (r.to(torch.float32).contiguous().view(torch.int32) & -65536).view(torch.float32).to(F64)
+
+
+def bf16_half_ulp(v: torch.Tensor) -> torch.Tensor:
+    """half an ulp of bf16 at the magnitude v >= 0: 8 significant bits, so an ulp is 2^-7 of the binade's power of two and half of one is
+    2^(floor(log2 v) - 8) - between 2^-9 v (top of a binade) and 2^-8 v (bottom); 2^-134 in the denormal range; 0 at 0"""
+    ex = torch.frexp(v)[1].clamp_min(-125)                     # v = m 2^ex, m in [0.5, 1)
+    return torch.where(v > 0, torch.ldexp(torch.ones_like(v), ex - 9), torch.zeros_like(v))
+
+
+def bf16_store_bar(r: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """bar of a bf16 result whose fp32 value before the store is within e of r: ONE round-to-nearest of a value of magnitude at most
+    |r| + e moves it by at most half an ulp there - bf16_half_ulp(|r| + e) + e.  (2^-9 (|r| + e) + e is that only at the top of a binade: a
+    correctly rounded 1 + 0.9 x 2^-8 -> 1 is off by 1.8 x 2^-9.)  A store that truncates errs by up to a whole ulp and fails this."""
+    return bf16_half_ulp(r.abs() + e) + e
+
+
+# The product GELU (csrc/lp_common.h gelu_f2 / gelu_df2) is not erff + expf: the forward is Numerical Recipes' erfcc (a Chebyshev fit of
+# erfc, fractional error < 1.2e-7), the backward Abramowitz & Stegun 7.1.26 (absolute error < 1.5e-7) with one exponential for both terms.
+# The two functions below evaluate THE SAME FORMULAS in torch float32 on the CPU, one operation per rounding (no fused multiply-add, no
+# hardware reciprocal or exponential): an evaluation independent of the kernels, measured against float64 for the bars of the kernel test.
+def gelu_erfcc_f32(x: torch.Tensor) -> torch.Tensor:
+    x = x.to(torch.float32)
+    z = x.abs() * 0.70710678118654752
+    t = 1.0 / (z * 0.5 + 1.0)
+    p = t * 0.17087277 - 0.82215223
+    for c in (1.48851587, -1.13520398, 0.27886807, -0.18628806, 0.09678418, 0.37409196, 1.00002368, -1.26551223):
+        p = p * t + c
+    tail = t * 0.5 * torch.exp(p - z * z)
+    return x * torch.where(x < 0, tail, 1.0 - tail)
+
+
+def gelu_grad_as26_f32(x: torch.Tensor) -> torch.Tensor:
+    x = x.to(torch.float32)
+    t = 1.0 / (x.abs() * (0.3275911 * 0.70710678118654752) + 1.0)
+    e = torch.exp(x * x * -0.5)
+    p = t * 1.061405429 - 1.453152027
+    for c in (1.421413741, -0.284496736, 0.254829592):
+        p = p * t + c
+    tail = p * t * 0.5 * e
+    return x * 0.3989422804014327 * e + torch.where(x < 0, tail, 1.0 - tail)
