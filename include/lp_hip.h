@@ -55,8 +55,9 @@ enum { LP_TF_NONE = 0, LP_TF_SINGLE = 1, LP_TF_PER_FRAME = 2, LP_TF_PER_VIEW = 3
  * 148 = the multi-view labeled batch with its 3-D augmentation (lp_mv3d_*), 149 = lp_conv_last_resident,
  * 150 = the DINOv3 backbones: lp_rope_*, lp_vit_reg_tokens_*, the prefix-dropping lp_layernorm_ls_*_px (and their fp32 forms),
  * 151 = crop-zoom prediction: lp_bbox_from_keypoints, lp_bbox_smooth, lp_frames_crop_resize,
- * 152 = prediction metrics: lp_kp_metrics. */
-#define LP_HIP_ABI_VERSION 152
+ * 152 = prediction metrics: lp_kp_metrics,
+ * 153 = the SAM backbone: lp_window_partition / _unpartition, lp_vit_pos_tokens_*, lp_resid_out_* (and their fp32 forms). */
+#define LP_HIP_ABI_VERSION 153
 int lp_version(void);
 const char* lp_strerror(int code);
 
@@ -462,6 +463,16 @@ int lp_f32_rope_bwd(float* dqkv, int ld, int k_off, const float* table, const in
                     int head_dim, lp_stream_t stream);
 int lp_f32_vit_reg_tokens_fwd(const float* patch, const float* cls, const float* reg, int B, int R, int Np, int D, float* x, lp_stream_t stream);
 int lp_f32_vit_reg_tokens_bwd(const float* dx, int B, int R, int Np, int D, float* dpatch, float* dcls, float* dreg, lp_stream_t stream);
+/* the fp32 forms of lp_window_partition / _unpartition, lp_vit_pos_tokens_fwd / _bwd and lp_resid_out_fwd / _bwd (below): float rows;
+ * the residual add has no y (the features are x_out itself) */
+int lp_f32_window_partition(const float* src, int ld_src, int B, int gh, int gw, int ws, int cols, const float* fill, float* dst,
+                            lp_stream_t stream);
+int lp_f32_window_unpartition(const float* src, int B, int gh, int gw, int ws, int cols, float* dst, int ld_dst, float* pad_colsum_acc,
+                              lp_stream_t stream);
+int lp_f32_vit_pos_tokens_fwd(const float* patch, const float* pos, int B, int Np, int D, float* x, lp_stream_t stream);
+int lp_f32_vit_pos_tokens_bwd(const float* dx, int B, int Np, int D, float* dpatch, float* dpos, lp_stream_t stream);
+int lp_f32_resid_out_fwd(const float* x, const float* delta, size_t n, float* x_out, lp_stream_t stream);
+int lp_f32_resid_out_bwd(const float* dy, size_t n, float* dx, lp_stream_t stream);
 int lp_f32_gelu_fwd(const float* x, size_t n, float* y, lp_stream_t stream);
 int lp_f32_gelu_bwd(const float* x, const float* dy, size_t n, float* dx, lp_stream_t stream);
 int lp_f32_attn_fwd(const float* qkv, int ld, int k_off, int v_off, int B, int nh, int T, float scale, float* p, float* o, int ldo,
@@ -689,6 +700,38 @@ int lp_rope_bwd(void* dqkv_bf16, int ld, int k_off, const float* table, const in
                 int head_dim, lp_stream_t stream);
 int lp_vit_reg_tokens_fwd(const void* patch_bf16, const float* cls, const float* reg, int B, int R, int Np, int D, float* x, lp_stream_t stream);
 int lp_vit_reg_tokens_bwd(const float* dx, int B, int R, int Np, int D, void* dpatch_bf16, float* dcls, float* dreg, lp_stream_t stream);
+/* The SAM backbone ("vitb_sam", transformers SamVisionEncoder with relative positions off and without its neck): csrc/window.hip.
+ *
+ * Window layers attend inside ws x ws windows of the (gh, gw) token grid, zero-padded on the bottom and right to nWy * ws x nWx * ws
+ * (nWy = ceil(gh / ws), nWx = ceil(gw / ws), nW = nWy * nWx).  Window b * nW + wy * nWx + wx holds, as its token ty * ws + tx, the grid
+ * position (wy * ws + ty, wx * ws + tx) of image b; a position outside the grid is a pad row.  The attention entry points then run
+ * unchanged on B * nW sequences of ws * ws tokens.
+ *
+ * lp_window_partition: dst[(B * nW * ws * ws)][cols] (dense) gathered from src[(b * gh + gy) * gw + gx][...] (rows ld_src elements apart,
+ *   ld_src >= cols).  Pad rows are copies of fill[cols] - for the fused qkv tensor: the qkv bias as the GEMM's store pass rounds it, because a
+ *   padded token is zero after the LayerNorm and still takes part in its window's soft-max - or zeros when fill is NULL (gradients).
+ * lp_window_unpartition: the inverse move, dst[(b * gh + gy) * gw + gx][0 .. cols) (rows ld_dst apart; columns behind cols untouched) from the
+ *   dense window rows; pad rows are dropped.  With pad_colsum_acc != NULL, pad_colsum_acc[c] += sum over ALL pad rows of src[.][c], in fp32:
+ *   the pad rows' dK / dV are gradient of the qkv bias.  ADDED to what the vector holds, once per call (with no pad rows it is left
+ *   untouched), in an order fixed by the shapes alone - 64 row slots take the pad positions 64 apart in ascending order, then the slots are
+ *   added in ascending order - with no atomics: the same inputs give the same bits.
+ * Both are moves of 16-byte pieces: every bit pattern (NaN payloads, -0.0) arrives unchanged; one launch each, nothing read back.
+ * LP_ERR_ARGUMENT: a null src / dst, a non-positive size, ws < 1, a pitch below cols - nothing is written.  LP_ERR_UNSUPPORTED: cols or the
+ * pitch not a multiple of 16 bytes, or src / dst / fill not 16-byte aligned.
+ *
+ * lp_vit_pos_tokens_fwd / _bwd: tokens without a prefix row, x[b][p] = float(patch[b * Np + p]) + pos[p] (pos (Np, D) fp32, D % 8 == 0);
+ *   backward: dpatch = bf16(dx), dpos[p] = sum_b dx[b][p] - images in ascending order, WRITTEN (not accumulated), as lp_vit_reg_tokens_bwd.
+ * lp_resid_out_fwd / _bwd: the residual add behind the last layer of a model without a final LayerNorm, x_out = x + float(delta) (x_out may be
+ *   x) and y = bf16(x_out), the features the head reads (n elements, n % 8 == 0);  backward: dx = float(dy), WRITTEN - the stream gradient
+ *   starts as the head's gradient. */
+int lp_window_partition(const void* src_bf16, int ld_src, int B, int gh, int gw, int ws, int cols, const void* fill_bf16, void* dst_bf16,
+                        lp_stream_t stream);
+int lp_window_unpartition(const void* src_bf16, int B, int gh, int gw, int ws, int cols, void* dst_bf16, int ld_dst, float* pad_colsum_acc,
+                          lp_stream_t stream);
+int lp_vit_pos_tokens_fwd(const void* patch_bf16, const float* pos, int B, int Np, int D, float* x, lp_stream_t stream);
+int lp_vit_pos_tokens_bwd(const float* dx, int B, int Np, int D, void* dpatch_bf16, float* dpos, lp_stream_t stream);
+int lp_resid_out_fwd(const float* x, const void* delta_bf16, size_t n, float* x_out, void* y_bf16, lp_stream_t stream);
+int lp_resid_out_bwd(const void* dy_bf16, size_t n, float* dx, lp_stream_t stream);
 /* in place: s[r][:n] = softmax(scale * s[r][:n]), s[r][n:ld] = 0   /   dp <- scale * p * (dp - sum(dp * p)) */
 int lp_softmax_rows_fwd(void* s_bf16, int rows, int n, int ld, float scale, lp_stream_t stream);
 int lp_softmax_rows_bwd(const void* p_bf16, void* dp_bf16, int rows, int n, int ld, float scale, lp_stream_t stream);

@@ -77,7 +77,7 @@ AUG_LOCAL_BLUR_COARSE, AUG_LOCAL_EMBOSS = 0, 1
 AUG_ELASTIC_MAX_RADIUS = 20
 TF_NONE, TF_SINGLE, TF_PER_FRAME, TF_PER_VIEW = 0, 1, 2, 3
 
-ABI_VERSION = 152   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
+ABI_VERSION = 153   # include/lp_hip.h: LP_HIP_ABI_VERSION - the header these PROTOTYPES were written against (tests/test_abi_and_failloud.py)
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 
@@ -184,6 +184,12 @@ PROTOTYPES = {
     "lp_rope_bwd": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lp_vit_reg_tokens_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "lp_vit_reg_tokens_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "lp_window_partition": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "lp_window_unpartition": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "lp_vit_pos_tokens_fwd": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "lp_vit_pos_tokens_bwd": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "lp_resid_out_fwd": (_I, [_P, _P, _Z, _P, _P, _P]),
+    "lp_resid_out_bwd": (_I, [_P, _Z, _P, _P]),
     "lp_softmax_rows_fwd": (_I, [_P, _I, _I, _I, _F, _P]),
     "lp_softmax_rows_bwd": (_I, [_P, _P, _I, _I, _I, _F, _P]),
     "lp_transpose_batched": (_I, [_P, _I, _I, _I, C.c_longlong, C.c_longlong, _P, _I, C.c_longlong, C.c_longlong, _I, _I, _P]),
@@ -235,6 +241,12 @@ PROTOTYPES = {
     "lp_f32_rope_bwd": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lp_f32_vit_reg_tokens_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "lp_f32_vit_reg_tokens_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "lp_f32_window_partition": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "lp_f32_window_unpartition": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "lp_f32_vit_pos_tokens_fwd": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "lp_f32_vit_pos_tokens_bwd": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "lp_f32_resid_out_fwd": (_I, [_P, _P, _Z, _P, _P]),
+    "lp_f32_resid_out_bwd": (_I, [_P, _Z, _P, _P]),
     "lp_f32_gelu_fwd": (_I, [_P, _Z, _P, _P]),
     "lp_f32_gelu_bwd": (_I, [_P, _P, _Z, _P, _P]),
     "lp_f32_attn_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P]),

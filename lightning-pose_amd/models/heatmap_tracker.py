@@ -24,6 +24,7 @@ from .backbones._init import head_state_dict, seeded_state_dict, vit_seeded_stat
 from .backbones.dinov2 import dinov2_seeded_state_dict, load_dinov2_checkpoint
 from .backbones.dinov3 import HF_NAMES as DINOV3_HF_NAMES, dinov3_seeded_state_dict, load_dinov3_checkpoint
 from .backbones.factory import DINOV2_CONFIGS, DINOV3_CONFIGS, VIT_CONFIGS
+from .backbones.sam import HF_NAMES as SAM_HF_NAMES, SAM_CONFIGS, load_sam_checkpoint, sam_seeded_state_dict
 from .base import BaseSupervisedTracker, SemiSupervisedTrackerMixin
 from .datatypes import HeatmapTrackerLabeledOutputsDict, HeatmapTrackerUnlabeledOutputsDict
 from .heads.heatmap import HeatmapHead, _Holder
@@ -78,7 +79,25 @@ class HeatmapTracker(BaseSupervisedTracker):
                                 downsample_factor=downsample_factor, _bound=True)
         self.backbone = _Holder()
         checkpoint = kwargs.get("backbone_checkpoint")
-        if backbone in VIT_CONFIGS or backbone in DINOV2_CONFIGS or backbone in DINOV3_CONFIGS:
+        if backbone in SAM_CONFIGS:
+            # transformers SamVisionEncoder as the reference's VisionEncoderSam runs it (vit_engine.py, arch="sam"): windowed attention, no
+            # [CLS], no final LayerNorm, and a position table resized once to the fine-tuning grid - ``image_size`` (reference default 256)
+            from ..vit_engine import ViTEngine as engine_cls
+            if self.precision == "fp32":  # validation mode (vit_engine_fp32.py)
+                from ..vit_engine_fp32 import Fp32ViTEngine as engine_cls
+            hidden, depth, heads, mlp, patch, window, global_layers, grid0, neck = SAM_CONFIGS[backbone]
+            image_size = int(kwargs.get("image_size") or 256)
+            self.net = engine_cls(num_keypoints, downsample_factor, device, hidden=hidden, depth=depth, heads=heads, mlp=mlp, patch=patch,
+                                  arch="sam", window=window, global_layers=global_layers, image_size=image_size, pretrain_grid=grid0,
+                                  neck_channels=neck)
+            init = sam_seeded_state_dict(hidden, depth, heads, mlp, patch, window, global_layers, grid0, neck, image_size // patch)
+            init.update(head_state_dict(self.num_fc_input_features, num_keypoints, self.head.n_layers))
+            if pretrained:
+                if checkpoint is None:
+                    raise RuntimeError("pretrained=True needs the SAM weights, which cannot be downloaded here; pass backbone_checkpoint="
+                                       f"<state_dict / safetensors file of {SAM_HF_NAMES[backbone]}> or pretrained=False")
+                load_sam_checkpoint(str(checkpoint), init)
+        elif backbone in VIT_CONFIGS or backbone in DINOV2_CONFIGS or backbone in DINOV3_CONFIGS:
             from ..vit_engine import ViTEngine
             dinov2, dinov3 = backbone in DINOV2_CONFIGS, backbone in DINOV3_CONFIGS
             # (the last field: the pretraining grid of the position table; DINOv3 has no table - its register-token count sits there)

@@ -33,6 +33,7 @@ from .ops import _p
 LN_EPS = 1e-12  # ViTConfig.layer_norm_eps
 DINOV2_LN_EPS = 1e-6  # Dinov2Config.layer_norm_eps
 DINOV3_LN_EPS = 1e-5  # DINOv3ViTConfig.layer_norm_eps
+SAM_LN_EPS = 1e-6     # SamVisionConfig.layer_norm_eps
 
 
 def bicubic_matrix(n_in: int, n_out: int) -> np.ndarray:
@@ -75,9 +76,17 @@ class LNP:
 
 class ViTPlan:
     def __init__(self, num_keypoints: int, downsample_factor: int, D: int, depth: int, heads: int, mlp: int, patch: int, n_pos: int,
-                 num_views: int = 0, arch: str = "vit", registers: int = 0):
+                 num_views: int = 0, arch: str = "vit", registers: int = 0, window: int = 0, global_layers: tuple[int, ...] = (),
+                 carried: tuple[tuple[str, tuple[int, ...]], ...] = ()):
         self.D, self.depth, self.heads, self.mlp, self.patch, self.n_pos = D, depth, heads, mlp, patch, n_pos
         self.arch, self.registers = arch, registers
+        # SAM: tensors of the reference's state_dict that nothing reads (rel_pos_*, neck.*) - (name, shape, offset) into a buffer of their
+        # own, outside the flat parameter / gradient buffers and so outside every optimiser group
+        self.carried, c_off = [], 0
+        for name, shape in carried:
+            self.carried.append((name, tuple(shape), c_off))
+            c_off += -(-math.prod(shape) // 4) * 4
+        self.n_carried = c_off
         pre = "backbone.vision_encoder"
         off = wd = 0
         # multi-view mode: the (V, D) view embeddings lead the flat buffers.  Their gradient is, with the other embeddings', the LAST to
@@ -105,7 +114,7 @@ class ViTPlan:
             off += D
             return off - D
 
-        self.cls_off = vec()
+        self.cls_off = None if arch == "sam" else vec()   # (SAM: no [CLS] token - the tokens are the patches)
         # DINOv2 (transformers Dinov2Model): embeddings.mask_token (1, D), which the forward pass never reads, and per layer the two
         # LayerScale vectors - all inside the backbone's range, each layer's own parameters still one contiguous run (grad_progress)
         self.mask_off = vec() if arch in ("dinov2", "dinov3") else None
@@ -115,9 +124,20 @@ class ViTPlan:
         off += registers * D
         self.pos_off = off
         off += n_pos * D
-        self.patch_lin = lin(f"{pre}.embeddings.patch_embeddings" + ("" if arch == "dinov3" else ".projection"), D, 3 * patch * patch)
+        # SAM (transformers SamVisionEncoder): ``pos_embed`` (1, g, g, D) at the fine-tuning grid (n_pos = g * g, no [CLS] row), ``patch_embed``,
+        # ``layers.{i}`` with ONE fused ``attn.qkv`` Linear (columns [q | k | v], head h at h * 64: the fused layout of every arch here),
+        # ``mlp.lin1`` / ``lin2``, and no final LayerNorm; "window": the layer's attention window (0: global)
+        patch_name = {"dinov3": "embeddings.patch_embeddings", "sam": "patch_embed.projection"}.get(arch, "embeddings.patch_embeddings.projection")
+        self.patch_lin = lin(f"{pre}.{patch_name}", D, 3 * patch * patch)
         self.layers = []
         for i in range(depth):
+            if arch == "sam":
+                p = f"{pre}.layers.{i}"
+                self.layers.append(dict(
+                    ln1=ln(f"{p}.layer_norm1"), qkv=lin(f"{p}.attn.qkv", 3 * D, D), proj=lin(f"{p}.attn.proj", D, D),
+                    ln2=ln(f"{p}.layer_norm2"), fc1=lin(f"{p}.mlp.lin1", mlp, D), fc2=lin(f"{p}.mlp.lin2", D, mlp),
+                    window=0 if i in global_layers else window))
+                continue
             if arch == "dinov3":
                 p = f"{pre}.model.layer.{i}"
                 self.layers.append(dict(
@@ -134,7 +154,7 @@ class ViTPlan:
             self.layers.append(dict(
                 ln1=ln(f"{p}.layernorm_before"), qkv=lin(f"{p}.attention.qkv", 3 * D, D), proj=lin(f"{p}.attention.o_proj", D, D),
                 ln2=ln(f"{p}.layernorm_after"), fc1=lin(f"{p}.mlp.fc1", mlp, D), fc2=lin(f"{p}.mlp.fc2", D, mlp)))
-        self.lnf = ln(f"{pre}.norm" if arch == "dinov3" else f"{pre}.layernorm")
+        self.lnf = None if arch == "sam" else ln(f"{pre}.norm" if arch == "dinov3" else f"{pre}.layernorm")
         self.n_backbone = off
         self.head: list[ConvP] = build_head(D, patch, num_keypoints, downsample_factor)
         self.convs: list[ConvP] = list(self.head)
@@ -158,7 +178,7 @@ class ViTPlan:
         out = []
         for L in self.layers:
             out += [L["ln1"], L["ln2"]]
-        return out + [self.lnf]
+        return out + ([self.lnf] if self.lnf is not None else [])
 
 
 class ViTEngine(EngineCore):
@@ -183,7 +203,18 @@ class ViTEngine(EngineCore):
     parameter and stays exactly 0.  ``pretrain_grid`` does not apply (there is no table to resize) and must be left unset.  In a training
     forward the patch coordinates are drawn anew per part of the pass (``pos_embed_shift`` / ``_jitter`` / ``_rescale``, the released
     configs' rescale 2.0 by default) from the engine's own seeded generator; ``forward(..., rope=draws)`` replays given draws, and
-    ``tape.meta["rope"]`` holds the ones a pass used.  Single-view only."""
+    ``tape.meta["rope"]`` holds the ones a pass used.  Single-view only.
+
+    ``arch="sam"`` is transformers' ``SamVisionEncoder`` as the reference's ``VisionEncoderSam`` runs it ("vitb_sam"):
+    relative positions off, the neck skipped, ``pos_embed`` at exactly the fine-tuning grid (``image_size`` // patch squared - any other
+    input size is an error), LayerNorm eps 1e-6, no [CLS] token and no final LayerNorm (``lp_vit_pos_tokens_*``, ``lp_resid_out_*``).
+    Every layer outside ``global_layers`` attends inside ``window`` x ``window`` windows of the zero-padded token grid:
+    ``lp_window_partition`` gathers the fused qkv tensor into B * nW sequences of window^2 tokens - pad rows hold the qkv bias, which is
+    what a padded (zero) token projects to, and take part in the soft-max - the attention kernels run on those, ``lp_window_unpartition``
+    scatters the result back; backward the same two moves on d_attn and dqkv, the pad rows' dK / dV summed into the qkv bias gradient.
+    ``rel_pos_h`` / ``rel_pos_w`` of every layer ((2 * window - 1, 64), global layers (2 * ``pretrain_grid`` - 1, 64)) and ``neck.*``
+    (``neck_channels``) are in the reference's state_dict although nothing reads them: they are carried in a buffer of their own - in
+    ``state_dict()``, absent from ``grad_views()`` and the optimiser's ranges.  Single-view only."""
 
     # A/B switches (EngineCore.SWITCHES).  bias_fused: every LayerNorm / GELU backward leaves the column sums that are the next Linear
     # layer's bias gradient (0: the weight-gradient launches take them).  gelu_fused: GELU inside fc1's store pass and fc2's data gradient
@@ -194,22 +225,53 @@ class ViTEngine(EngineCore):
     _reg_token_kernels = ("lp_vit_reg_tokens_fwd", "lp_vit_reg_tokens_bwd")
     _rope_kernels = ("lp_rope_fwd", "lp_rope_bwd")
     _ln_px_kernels = ("lp_layernorm_ls_fwd_px", "lp_layernorm_ls_bwd_px")
-    _elem_bytes = 2.0    # of a token row's elements (the rope launches' byte counts)
+    _window_kernels = ("lp_window_partition", "lp_window_unpartition")
+    _pos_token_kernels = ("lp_vit_pos_tokens_fwd", "lp_vit_pos_tokens_bwd")
+    _act_dtype = torch.bfloat16   # of the activations between the kernels
+    _elem_bytes = 2.0    # of a token row's elements (the rope and window launches' byte counts)
 
     def __init__(self, num_keypoints: int, downsample_factor: int = 2, device: torch.device | str = "cuda:0", hidden: int = 384,
                  depth: int = 12, heads: int = 6, mlp: int = 1536, patch: int = 16, pretrain_grid: int | None = None, num_views: int = 0,
                  arch: str = "vit", registers: int | None = None, rope_theta: float = 100.0, pos_embed_shift: float | None = None,
-                 pos_embed_jitter: float | None = None, pos_embed_rescale: float | None = 2.0, rope_seed: int = 0):
+                 pos_embed_jitter: float | None = None, pos_embed_rescale: float | None = 2.0, rope_seed: int = 0, window: int | None = None,
+                 global_layers: tuple[int, ...] | None = None, image_size: int | None = None, neck_channels: int = 256):
         if hidden % 64 or (hidden // heads) != 64 or mlp % 64:
             raise NotImplementedError("ViT widths must be multiples of 64 with 64-wide heads (ViT-S/B)")
         if num_views < 0:
             raise ValueError(f"num_views must be positive (0: single-view tokens with [CLS]), got {num_views}")
-        if arch not in ("vit", "dinov2", "dinov3"):
-            raise ValueError(f'arch must be "vit", "dinov2" or "dinov3", got {arch!r}')
+        if arch not in ("vit", "dinov2", "dinov3", "sam"):
+            raise ValueError(f'arch must be "vit", "dinov2", "dinov3" or "sam", got {arch!r}')
         if arch != "vit" and num_views:
             raise NotImplementedError("the multi-view token assembly (num_views > 0) is not implemented for the "
-                                      f"{'DINOv2' if arch == 'dinov2' else 'DINOv3'} backbones")
-        if arch == "dinov3":
+                                      f"{ {'dinov2': 'DINOv2', 'dinov3': 'DINOv3', 'sam': 'SAM'}[arch]} backbones")
+        if arch != "sam" and (window is not None or global_layers is not None or image_size is not None):
+            raise ValueError(f'window / global_layers / image_size belong to arch="sam", got them with arch={arch!r}')
+        carried: list[tuple[str, tuple[int, ...]]] = []
+        if arch == "sam":
+            if registers:
+                raise ValueError(f'register tokens belong to arch="dinov3", got registers={registers} with arch="sam"')
+            if image_size is None or image_size <= 0 or image_size % patch:
+                raise ValueError(f'arch="sam" needs image_size, a positive multiple of the patch size {patch}: its position table is resized '
+                                 f"once, to the fine-tuning grid, and trained at that size; got image_size={image_size}")
+            window = 14 if window is None else int(window)
+            if window < 1:
+                raise ValueError(f"window must be >= 1, got {window}")
+            global_layers = (2, 5, 8, 11) if global_layers is None else tuple(int(i) for i in global_layers)
+            if any(not 0 <= i < depth for i in global_layers):
+                raise ValueError(f"global_layers must name layers in [0, {depth}), got {global_layers}")
+            registers = 0
+            pretrain_grid = 64 if pretrain_grid is None else int(pretrain_grid)   # (only the shapes of the carried rel_pos_* depend on it)
+            self.sam_grid = image_size // patch
+            n_pos = self.sam_grid * self.sam_grid
+            pre = "backbone.vision_encoder"
+            for i in range(depth):
+                n_rel = 2 * (pretrain_grid if i in global_layers else window) - 1
+                carried += [(f"{pre}.layers.{i}.attn.rel_pos_h", (n_rel, hidden // heads)), (f"{pre}.layers.{i}.attn.rel_pos_w", (n_rel, hidden // heads))]
+            nc = int(neck_channels)
+            carried += [(f"{pre}.neck.conv1.weight", (nc, hidden, 1, 1)), (f"{pre}.neck.layer_norm1.weight", (nc,)),
+                        (f"{pre}.neck.layer_norm1.bias", (nc,)), (f"{pre}.neck.conv2.weight", (nc, nc, 3, 3)),
+                        (f"{pre}.neck.layer_norm2.weight", (nc,)), (f"{pre}.neck.layer_norm2.bias", (nc,))]
+        elif arch == "dinov3":
             if pretrain_grid is not None:
                 raise ValueError('arch="dinov3" has no position table (its positions are rotary): pretrain_grid does not apply')
             registers = 4 if registers is None else int(registers)
@@ -222,11 +284,13 @@ class ViTEngine(EngineCore):
             registers = 0
             pretrain_grid = 14 if pretrain_grid is None else pretrain_grid
             n_pos = 1 + pretrain_grid * pretrain_grid
-        super().__init__(ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, n_pos, num_views, arch, registers),
+        super().__init__(ViTPlan(num_keypoints, downsample_factor, hidden, depth, heads, mlp, patch, n_pos, num_views, arch, registers,
+                                 window=window or 0, global_layers=tuple(global_layers or ()), carried=tuple(carried)),
                          num_keypoints, downsample_factor, device)
         self.grid0 = pretrain_grid
         self.arch = arch
-        self.ln_eps = {"dinov2": DINOV2_LN_EPS, "dinov3": DINOV3_LN_EPS}.get(arch, LN_EPS)
+        self.ln_eps = {"dinov2": DINOV2_LN_EPS, "dinov3": DINOV3_LN_EPS, "sam": SAM_LN_EPS}.get(arch, LN_EPS)
+        self.carried = torch.zeros(self.plan.n_carried, device=self.device, dtype=torch.float32)   # (SAM: rel_pos_* / neck.*, never read)
         # rotary positions (DINOv3): the table of a grid is built on the host with DINOv3ViTRopePositionEmbedding's own torch operations
         self.rope_theta = float(rope_theta)
         self.rope_aug = dict(shift=pos_embed_shift, jitter=pos_embed_jitter, rescale=pos_embed_rescale)
@@ -247,10 +311,13 @@ class ViTEngine(EngineCore):
         pl, D = self.plan, self.plan.D
         pre = "backbone.vision_encoder"
         sd = {"view_embeddings": buf[pl.view_off:pl.n_view].view(pl.num_views, D)} if pl.num_views else {}
-        sd[f"{pre}.embeddings.cls_token"] = buf[pl.cls_off:pl.cls_off + D].view(1, 1, D)
+        if pl.cls_off is not None:
+            sd[f"{pre}.embeddings.cls_token"] = buf[pl.cls_off:pl.cls_off + D].view(1, 1, D)
         if pl.mask_off is not None:
             sd[f"{pre}.embeddings.mask_token"] = buf[pl.mask_off:pl.mask_off + D].view(*((1, 1, D) if pl.arch == "dinov3" else (1, D)))
-        if pl.arch == "dinov3":
+        if pl.arch == "sam":
+            sd[f"{pre}.pos_embed"] = buf[pl.pos_off:pl.pos_off + pl.n_pos * D].view(1, self.sam_grid, self.sam_grid, D)
+        elif pl.arch == "dinov3":
             sd[f"{pre}.embeddings.register_tokens"] = buf[pl.reg_off:pl.reg_off + pl.registers * D].view(1, pl.registers, D)
         else:
             sd[f"{pre}.embeddings.position_embeddings"] = buf[pl.pos_off:pl.pos_off + pl.n_pos * D].view(1, pl.n_pos, D)
@@ -281,7 +348,10 @@ class ViTEngine(EngineCore):
         return sd
 
     def state_dict(self) -> dict[str, torch.Tensor]:
-        return self._views(self.P)
+        sd = self._views(self.P)
+        for name, shape, off in self.plan.carried:   # (SAM: loaded and saved unchanged; no gradient view, no optimiser range)
+            sd[name] = self.carried[off:off + math.prod(shape)].view(shape)
+        return sd
 
     def grad_views(self) -> dict[str, torch.Tensor]:
         return self._views(self.G)
@@ -447,6 +517,8 @@ class ViTEngine(EngineCore):
         """(1 + gh*gw, D) position embeddings: the [CLS] row + the pretraining grid resized bicubically (HF interpolate_pos_encoding)"""
         pl, D = self.plan, self.plan.D
         pos = self.P[pl.pos_off:pl.pos_off + pl.n_pos * D].view(pl.n_pos, D)
+        if pl.arch == "sam":   # (gh * gw, D), no [CLS] row: the table IS the fine-tuning grid (_forward refuses every other input size)
+            return pos
         if gh == self.grid0 and gw == self.grid0:
             return pos
         key = (gh, gw)
@@ -530,25 +602,59 @@ class ViTEngine(EngineCore):
         D = self.plan.D
         self.G[l.b_off + D:l.b_off + 2 * D].zero_()
 
+    # ------------------------------------------------------------------------------------------------ windows (SAM)
+    @staticmethod
+    def window_rows(B: int, gh: int, gw: int, ws: int) -> tuple[int, int]:
+        """(sequences, tokens per sequence) of a window layer: B * nW windows of ws * ws tokens over the zero-padded grid"""
+        return B * (-(-gh // ws)) * (-(-gw // ws)), ws * ws
+
+    def _qkv_pad_fill(self, l: Lin) -> torch.Tensor:
+        """what the qkv Linear's store pass writes for an all-zero input row: the bias, rounded as that pass rounds it (the operand copy)"""
+        return self.Wb[l.b_off:l.b_off + l.N]
+
+    def _win_part(self, t: torch.Tensor, ld: int, cols: int, B: int, gh: int, gw: int, ws: int, fill: torch.Tensor | None) -> torch.Tensor:
+        """grid layout (B * gh * gw rows, pitch ``ld``) -> window layout (B * nW * ws^2, cols); pad rows = ``fill`` (None: zeros)"""
+        nseq, nt = self.window_rows(B, gh, gw, ws)
+        out = torch.empty(nseq * nt, cols, device=self.device, dtype=self._act_dtype)
+        name = self._window_kernels[0]
+        self._timed("window_partition_kernel", 0.0, lambda: check(getattr(self._lib, name)(
+            _p(t), ld, B, gh, gw, ws, cols, _p(fill), _p(out), ops._stream()), name),
+            nbytes=self._elem_bytes * cols * (B * gh * gw + nseq * nt))   # real rows read once, every window row written once
+        return out
+
+    def _win_unpart(self, tw: torch.Tensor, cols: int, B: int, gh: int, gw: int, ws: int, pad_colsum: torch.Tensor | None = None) -> torch.Tensor:
+        """window layout -> grid layout (B * gh * gw, cols); ``pad_colsum``: the pad rows' column sums are ADDED there (fp32)"""
+        nseq, nt = self.window_rows(B, gh, gw, ws)
+        out = torch.empty(B * gh * gw, cols, device=self.device, dtype=self._act_dtype)
+        name = self._window_kernels[1]
+        rows_read = nseq * nt if pad_colsum is not None else B * gh * gw
+        self._timed("window_unpartition_kernel", 0.0, lambda: check(getattr(self._lib, name)(
+            _p(tw), B, gh, gw, ws, cols, _p(out), cols, _p(pad_colsum), ops._stream()), name),
+            nbytes=self._elem_bytes * cols * (rows_read + B * gh * gw))
+        return out
+
     # ------------------------------------------------------------------------------------------------ tokens
     def _seq(self, parts: list[torch.Tensor], Np: int) -> tuple[int, int, int]:
         """(sequences, tokens per sequence, ``drop_T`` of the final LayerNorm) for these batches of images with Np patches each"""
         V = self.plan.num_views
         B = sum(p_.shape[0] for p_ in parts)
         if not V:   # one sequence per image, [CLS] (and DINOv3's registers: self.n_prefix rows) in front and dropped in front of the head
-            return B, Np + self.n_prefix, Np + self.n_prefix
+            return B, Np + self.n_prefix, (Np + self.n_prefix if self.n_prefix else 0)   # (SAM: no prefix, no final LayerNorm)
         if any(p_.shape[0] % V for p_ in parts):
             raise ValueError(f"a multi-view batch holds num_views = {V} images per sample, got {[p_.shape[0] for p_ in parts]} images")
         return B // V, V * Np, 0                # one sequence per sample: the patches of all its views, nothing dropped
 
     @property
     def n_prefix(self) -> int:
-        """rows in front of the patch tokens of a single-view sequence: [CLS] and the register tokens"""
-        return 1 + self.plan.registers
+        """rows in front of the patch tokens of a single-view sequence: [CLS] and the register tokens (SAM: none)"""
+        return 0 if self.plan.arch == "sam" else 1 + self.plan.registers
 
     def _tokens_fwd(self, pe: torch.Tensor, pos: torch.Tensor | None, B: int, Np: int, x: torch.Tensor) -> None:
         pl, (fwd, _, mv_fwd, _) = self.plan, self._token_kernels
-        if pl.arch == "dinov3":   # [CLS], the registers, the patch embeddings: nothing is added to the tokens
+        if pl.arch == "sam":   # patch embeddings + position table, no prefix rows
+            fwd = self._pos_token_kernels[0]
+            check(getattr(self._lib, fwd)(_p(pe), _p(pos), B, Np, pl.D, _p(x), ops._stream()), fwd)
+        elif pl.arch == "dinov3":   # [CLS], the registers, the patch embeddings: nothing is added to the tokens
             fwd = self._reg_token_kernels[0]
             check(getattr(self._lib, fwd)(_p(pe), _p(self.P[pl.cls_off:]), _p(self.P[pl.reg_off:]) if pl.registers else None, B, pl.registers, Np,
                                           pl.D, _p(x), ops._stream()), fwd)
@@ -564,6 +670,12 @@ class ViTEngine(EngineCore):
         pl, D, dev = self.plan, self.plan.D, self.device
         _, bwd, _, mv_bwd = self._token_kernels
         dpatch = torch.empty(B * Np, D, device=dev, dtype=self._patch_dtype)
+        if pl.arch == "sam":   # the kernel WRITES the sums over the images; added to G here, at the table's own grid (nothing to interpolate)
+            bwd = self._pos_token_kernels[1]
+            dpos = torch.empty(Np, D, device=dev, dtype=torch.float32)
+            check(getattr(self._lib, bwd)(_p(dx), B, Np, D, _p(dpatch), _p(dpos), ops._stream()), bwd)
+            self.G[pl.pos_off:pl.pos_off + Np * D] += dpos.view(-1)
+            return dpatch
         if pl.arch == "dinov3":   # the kernel WRITES the sums over the images; they are added to G here (a backward pass accumulates)
             R, bwd = pl.registers, self._reg_token_kernels[1]
             dpre = torch.empty(1 + R, D, device=dev, dtype=torch.float32)
@@ -612,9 +724,10 @@ class ViTEngine(EngineCore):
         D, nh, pt = pl.D, pl.heads, pl.patch
         parts, B, H, W = image_parts(images, pt, None, of="the patch size ")
         gh, gw = H // pt, W // pt
+        self._check_sam_input(H, W)
         Np = gh * gw
         Bs, Tn, drop_T = self._seq(parts, Np)   # (B images; the layers see Bs sequences of Tn tokens)
-        M, Tp = Bs * Tn, -(-Tn // 64) * 64
+        M = Bs * Tn
         tp = Tape()
         T = tp.t
         dev = self.device
@@ -642,14 +755,25 @@ class ViTEngine(EngineCore):
             qkv = self._linear(y1, L["qkv"], M)
             if rope_tab is not None:   # DINOv3: the patch tokens' q and k rotated in place; the tape keeps the rotated q and k, which is
                 self._rope(0, qkv, qs, rope_tab, rope_seq, n_tab, Bs, Tn)   # what lp_attn_bwd_kv and dQ = dS K need
+            # SAM's window layers: the attention sees aB windows of aT tokens, gathered from the qkv tensor AFTER the GEMM - the pad rows are
+            # the qkv bias, so the GEMM itself runs on the real tokens only; the tape keeps the windowed qkv (what the backward kernels read)
+            ws = L.get("window", 0)
+            aB, aT = self.window_rows(B, gh, gw, ws) if ws else (Bs, Tn)
+            if ws:
+                qkv = self._win_part(qkv, qs, qs, B, gh, gw, ws, self._qkv_pad_fill(L["qkv"]))
+            Tp = -(-aT // 64) * 64
             # P = softmax(Q K^T / 8) (bf16, row pitch Tp, pad columns zero; kept for the backward pass) and attn = P V in one kernel:
             # the scores themselves never reach memory
-            S = torch.empty(Bs * nh * Tn, Tp, device=dev, dtype=torch.bfloat16) if keep else None
-            attn = torch.empty(M, D, device=dev, dtype=torch.bfloat16)
+            S = torch.empty(aB * nh * aT, Tp, device=dev, dtype=torch.bfloat16) if keep else None
+            attn = torch.empty(aB * aT, D, device=dev, dtype=torch.bfloat16)
             # scores + probabilities x values: 2 products of B * nh * Tn * Tn * (D / nh) MACs; the training pass computes the scores twice
-            self._timed("attn_fwd_kernel", 4.0 * Bs * Tn * Tn * D, lambda: check(self._lib.lp_attn_fwd(
-                _p(qkv), qs, D, 2 * D, Bs, nh, Tn, scale, _p(S), Tp, _p(attn), D, ops._stream()), "lp_attn_fwd"),
-                nbytes=2.0 * (3 * Bs * Tn * D + Bs * Tn * D) + (2.0 * Bs * nh * Tn * Tp if S is not None else 0.0))
+            self._timed("attn_fwd_kernel", 4.0 * aB * aT * aT * D, lambda: check(self._lib.lp_attn_fwd(
+                _p(qkv), qs, D, 2 * D, aB, nh, aT, scale, _p(S), Tp, _p(attn), D, ops._stream()), "lp_attn_fwd"),
+                nbytes=2.0 * (3 * aB * aT * D + aB * aT * D) + (2.0 * aB * nh * aT * Tp if S is not None else 0.0))
+            if ws:
+                if keep:
+                    T[f"l{i}.attn_w"] = attn   # (lp_attn_rowdot pairs it with the windowed d_attn)
+                attn = self._win_unpart(attn, D, B, gh, gw, ws)
             proj = self._linear(attn, L["proj"], M)
             x_in = x
             y2, m2, r2, x = self._ln(x, proj, L["ln2"], M, ls=L.get("ls1"))
@@ -661,12 +785,25 @@ class ViTEngine(EngineCore):
                     T[f"l{i}.{nm}"] = v
                 if "ls1" in L:   # the unscaled branch outputs: the LayerScale gradients are taken against them
                     T[f"l{i}.proj"], T[f"l{i}.fc2"] = proj, delta
-        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"), n_prefix=self.n_prefix)
-        if keep:
-            T["x_last"], T["mf"], T["rf"] = x, mf, rf
+        if pl.lnf is None:   # SAM: no final LayerNorm - the last residual add alone, its sum is the features
+            feat = torch.empty(M, D, device=dev, dtype=torch.bfloat16)
+            x_last = torch.empty_like(x)   # (not in place: x is the last layer's x_mid, which its LayerNorm backward reads from the tape)
+            check(self._lib.lp_resid_out_fwd(_p(x), _p(delta), M * D, _p(x_last), _p(feat), ops._stream()), "lp_resid_out_fwd")
+        else:
+            feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"), n_prefix=self.n_prefix)
+            if keep:
+                T["x_last"], T["mf"], T["rf"] = x, mf, rf
         heat = self._head_forward(feat.view(B, gh, gw, D), B, gh, gw, T if keep else {})
         tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training, seq=(Bs, Tn, drop_T), rope=draws)
         return heat, tp
+
+    def _check_sam_input(self, H: int, W: int) -> None:
+        """SAM's position table was resized once, to the fine-tuning grid, and is trained at that size (reference vit_sam.py): an image of
+        another size, or a non-square one, has no table"""
+        if self.plan.arch == "sam" and (H != self.sam_grid * self.plan.patch or W != self.sam_grid * self.plan.patch):
+            side = self.sam_grid * self.plan.patch
+            raise ValueError(f'arch="sam" was built for {side} x {side} images (image_size={side}: its position table holds exactly that '
+                             f"grid); got {H} x {W}")
 
     # ------------------------------------------------------------------------------------------------ backward
     def backward(self, tp: Tape, g_heat: torch.Tensor, trace: dict | None = None) -> None:
@@ -675,7 +812,7 @@ class ViTEngine(EngineCore):
         D, nh = pl.D, pl.heads
         Np = gh * gw
         Bs, Tn, drop_T = tp.meta["seq"]
-        M, Tp = Bs * Tn, -(-Tn // 64) * 64
+        M = Bs * Tn
         dev = self.device
         self._wg_shape = (Bs, Tn)
         scale = 1.0 / math.sqrt(D // nh)
@@ -685,7 +822,8 @@ class ViTEngine(EngineCore):
         progress = self.grad_progress if (self.grad_progress is not None and self.single_backward) else None
         if progress is not None:
             progress(pl.n_backbone)  # the head's gradients (the tail of the flat buffer) are complete
-        dx = torch.zeros(M, D, device=dev, dtype=torch.float32)         # gradient of the residual stream
+        # gradient of the residual stream (SAM: lp_resid_out_bwd writes all of it)
+        dx = (torch.empty if pl.lnf is None else torch.zeros)(M, D, device=dev, dtype=torch.float32)
         # every LayerNorm backward also leaves the updated stream gradient in bf16: it is the operand of the next Linear backward
         # ... and its column sums are the bias gradient of that layer (fc2 of the last block here), so no weight gradient needs a bias pass
         fuse_bias = self.bias_fused
@@ -698,8 +836,14 @@ class ViTEngine(EngineCore):
                 return {}
             return dict(ls=pl.layers[j]["ls" + nm], branch=T[f"l{j}." + ("proj" if nm == "1" else "fc2")])
 
-        dx16 = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, colsum=bsum(pl.layers[-1]["fc2"]),
-                            n_prefix=self.n_prefix, **scaled(pl.depth - 1, "2"))
+        if pl.lnf is None:
+            # SAM: no final LayerNorm.  The head's gradient IS the operand of the last fc2's backward, and its fp32 copy starts the stream
+            # gradient; no walk has left that layer's bias sums, so its weight-gradient launch takes them (last_fc2_bias)
+            dx16 = d_feat.view(M, D)
+            check(self._lib.lp_resid_out_bwd(_p(dx16), M * D, _p(dx), ops._stream()), "lp_resid_out_bwd")
+        else:
+            dx16 = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True,
+                                colsum=bsum(pl.layers[-1]["fc2"]), n_prefix=self.n_prefix, **scaled(pl.depth - 1, "2"))
         rope_tab, rope_seq = T.get("rope_tab"), T.get("rope_seq")
 
         for i in range(pl.depth - 1, -1, -1):
@@ -709,11 +853,12 @@ class ViTEngine(EngineCore):
                 trace[f"l{i}.dout"] = dx.clone()
             # ---- MLP branch: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
             dmlp = dx16
+            fc2_bias_done = fuse_bias and not (pl.lnf is None and i == pl.depth - 1)
             if fuse_bias and fuse_gelu:   # GELU's backward inside fc2's data gradient (round 6): d_a1 is never written
-                d_h1 = self._linear_bwd(L["fc2"], t("a1"), dmlp, M, bias_done=True, gelu_of=(t("h1"), bsum(L["fc1"])))
+                d_h1 = self._linear_bwd(L["fc2"], t("a1"), dmlp, M, bias_done=fc2_bias_done, gelu_of=(t("h1"), bsum(L["fc1"])))
                 d_a1 = None
             else:
-                d_a1 = self._linear_bwd(L["fc2"], t("a1"), dmlp, M, bias_done=fuse_bias)
+                d_a1 = self._linear_bwd(L["fc2"], t("a1"), dmlp, M, bias_done=fc2_bias_done)
                 d_h1 = torch.empty_like(d_a1)
             if d_a1 is None:
                 pass
@@ -729,22 +874,32 @@ class ViTEngine(EngineCore):
             dproj = dx16
             d_attn = self._linear_bwd(L["proj"], t("attn"), dproj, M)
             qkv, Pm = t("qkv"), t("P")
-            dqkv = torch.empty(M, qs, device=dev, dtype=torch.bfloat16)
-            zP = (nh * Tn * Tp, Tn * Tp)       # batch strides of a [Bs][nh][Tn][Tp] tensor
+            # SAM's window layers: the same kernels on aB windows of aT tokens - d_attn gathered into windows (pad rows zero: a pad query's
+            # output was cropped, so its dS row and dQ are zero), dqkv scattered back behind them
+            ws = L.get("window", 0)
+            aB, aT = self.window_rows(B, gh, gw, ws) if ws else (Bs, Tn)
+            aM, Tp = aB * aT, -(-aT // 64) * 64
+            attn_o = t("attn")
+            if ws:
+                d_attn, attn_o = self._win_part(d_attn, D, D, B, gh, gw, ws, None), t("attn_w")
+            dqkv = torch.empty(aM, qs, device=dev, dtype=torch.bfloat16)
+            zP = (nh * aT * Tp, aT * Tp)       # batch strides of a [Bs][nh][Tn][Tp] tensor
             zT = (nh * 64 * Tp, 64 * Tp)       # ... of a [B][nh][64][Tp] transposed head slice
             # D = rowsum(dO o O) (== rowsum(dP o P) because O = P V), then ONE pass over the stored probabilities leaves
             # dS = scale * P o (dO V^T - D), dV = P^T dO and dK = dS^T Q (dP never exists; P and dS are touched once each here)
-            drow = torch.empty(M, nh, device=dev, dtype=torch.float32)
-            check(self._lib.lp_attn_rowdot(_p(d_attn), _p(t("attn")), M, nh, D, _p(drow), ops._stream()), "lp_attn_rowdot")
-            dS = torch.empty(Bs * nh * Tn, Tp, device=dev, dtype=torch.bfloat16)
+            drow = torch.empty(aM, nh, device=dev, dtype=torch.float32)
+            check(self._lib.lp_attn_rowdot(_p(d_attn), _p(attn_o), aM, nh, D, _p(drow), ops._stream()), "lp_attn_rowdot")
+            dS = torch.empty(aB * nh * aT, Tp, device=dev, dtype=torch.bfloat16)
             # dP = dO V^T, dV = P^T dO, dK = dS^T Q: 3 products of B * Tn * Tn * D MACs
-            self._timed("attn_bwd_kv_kernel", 6.0 * Bs * Tn * Tn * D, lambda: check(self._lib.lp_attn_bwd_kv(
-                _p(qkv), qs, 2 * D, _p(d_attn), D, _p(Pm), Tp, _p(drow), Bs, nh, Tn, scale, _p(dS), _p(dqkv), qs, D, 2 * D, ops._stream()),
-                "lp_attn_bwd_kv"), nbytes=2.0 * (2 * Bs * nh * Tn * Tp + 6 * Bs * Tn * D))
+            self._timed("attn_bwd_kv_kernel", 6.0 * aB * aT * aT * D, lambda: check(self._lib.lp_attn_bwd_kv(
+                _p(qkv), qs, 2 * D, _p(d_attn), D, _p(Pm), Tp, _p(drow), aB, nh, aT, scale, _p(dS), _p(dqkv), qs, D, 2 * D, ops._stream()),
+                "lp_attn_bwd_kv"), nbytes=2.0 * (2 * aB * nh * aT * Tp + 6 * aB * aT * D))
             # dQ = dS K
-            tmpT = torch.empty(Bs * nh * 64, Tp, device=dev, dtype=torch.bfloat16)      # a transposed [64][Tp] head slice
-            self._transpose(qkv[:, D:].data_ptr(), Tn, 64, qs, Tn * qs, 64, tmpT, Tp, *zT, Bs, nh)
-            self._gemm(_p(dS), Tp, _p(tmpT), Tp, Tn, 64, Tp, dqkv, qs, batch=(Bs, nh, *zP, *zT, Tn * qs, 64))
+            tmpT = torch.empty(aB * nh * 64, Tp, device=dev, dtype=torch.bfloat16)      # a transposed [64][Tp] head slice
+            self._transpose(qkv[:, D:].data_ptr(), aT, 64, qs, aT * qs, 64, tmpT, Tp, *zT, aB, nh)
+            self._gemm(_p(dS), Tp, _p(tmpT), Tp, aT, 64, Tp, dqkv, qs, batch=(aB, nh, *zP, *zT, aT * qs, 64))
+            if ws:   # the pad rows' dK / dV are gradient of the qkv bias (their k and v ARE the bias): summed into it by the same launch
+                dqkv = self._win_unpart(dqkv, qs, B, gh, gw, ws, pad_colsum=self.G[L["qkv"].b_off:L["qkv"].b_off + qs])
             if trace is not None:
                 trace[f"l{i}.dqkv"] = dqkv
             if rope_tab is not None:   # dqkv is complete: the transposed rotation of dQ / dK, before the qkv weight gradient reads it

@@ -31,7 +31,14 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
     _reg_token_kernels = ("lp_f32_vit_reg_tokens_fwd", "lp_f32_vit_reg_tokens_bwd")
     _rope_kernels = ("lp_f32_rope_fwd", "lp_f32_rope_bwd")
     _ln_px_kernels = ("lp_f32_layernorm_ls_fwd_px", "lp_f32_layernorm_ls_bwd_px")
+    _window_kernels = ("lp_f32_window_partition", "lp_f32_window_unpartition")
+    _pos_token_kernels = ("lp_f32_vit_pos_tokens_fwd", "lp_f32_vit_pos_tokens_bwd")
+    _act_dtype = torch.float32
     _elem_bytes = 4.0
+
+    def _qkv_pad_fill(self, l: Lin) -> torch.Tensor:
+        """an all-zero input row leaves the fp32 Linear layer as the bias itself"""
+        return self.P[l.b_off:l.b_off + l.N]
 
     @staticmethod
     def _lin_geom(l: Lin, M: int):
@@ -100,6 +107,7 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
         D, nh, pt = pl.D, pl.heads, pl.patch
         parts, B, H, W = image_parts(images, pt, None, of="the patch size ")
         gh, gw = H // pt, W // pt
+        self._check_sam_input(H, W)
         Np = gh * gw
         Bs, Tn, drop_T = self._seq(parts, Np)   # (B images; the layers see Bs sequences of Tn tokens)
         M = Bs * Tn
@@ -126,9 +134,15 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
             qkv = self._linear(y1, L["qkv"], M)
             if rope_tab is not None:   # DINOv3: the patch tokens' q and k rotated in place (the tape keeps them rotated)
                 self._rope(0, qkv, qs, rope_tab, rope_seq, n_tab, Bs, Tn)
-            Pm = self._f32(Bs * nh * Tn, Tn)
-            attn = self._f32(M, D)
-            check(self._lib.lp_f32_attn_fwd(_p(qkv), qs, D, 2 * D, Bs, nh, Tn, scale, _p(Pm), _p(attn), D, ops._stream()), "lp_f32_attn_fwd")
+            ws = L.get("window", 0)   # SAM's window layers: aB windows of aT tokens, pad rows = the qkv bias (vit_engine.py)
+            aB, aT = self.window_rows(B, gh, gw, ws) if ws else (Bs, Tn)
+            if ws:
+                qkv = self._win_part(qkv, qs, qs, B, gh, gw, ws, self._qkv_pad_fill(L["qkv"]))
+            Pm = self._f32(aB * nh * aT, aT)
+            attn = self._f32(aB * aT, D)
+            check(self._lib.lp_f32_attn_fwd(_p(qkv), qs, D, 2 * D, aB, nh, aT, scale, _p(Pm), _p(attn), D, ops._stream()), "lp_f32_attn_fwd")
+            if ws:
+                attn = self._win_unpart(attn, D, B, gh, gw, ws)
             proj = self._linear(attn, L["proj"], M)
             x_in = x
             y2, m2, r2, x = self._ln(x, proj, L["ln2"], M, ls=L.get("ls1"))
@@ -142,8 +156,12 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
                     T[f"l{i}.{nm}"] = v
                 if "ls1" in L:   # the unscaled branch outputs: the LayerScale gradients are taken against them
                     T[f"l{i}.proj"], T[f"l{i}.fc2"] = proj, delta
-        feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"), n_prefix=self.n_prefix)
-        T["x_last"], T["mf"], T["rf"] = x, mf, rf
+        if pl.lnf is None:   # SAM: no final LayerNorm - the features are the last residual add's sum
+            feat = self._f32(M, D)
+            check(self._lib.lp_f32_resid_out_fwd(_p(x), _p(delta), M * D, _p(feat), ops._stream()), "lp_f32_resid_out_fwd")
+        else:
+            feat, mf, rf, x = self._ln(x, delta, pl.lnf, M, drop_T=drop_T, ls=pl.layers[-1].get("ls2"), n_prefix=self.n_prefix)
+            T["x_last"], T["mf"], T["rf"] = x, mf, rf
         heat = self._head_forward(feat.view(B, gh, gw, D), B, gh, gw, T)
         tp.meta.update(B=B, H=H, W=W, gh=gh, gw=gw, training=training, seq=(Bs, Tn, drop_T), rope=draws)
         return heat, tp
@@ -158,15 +176,20 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
         scale = 1.0 / math.sqrt(D // nh)
         qs = 3 * D
         d_feat = self._head_backward(T, B, g_heat).contiguous()            # (B, gh, gw, D) fp32
-        dx = torch.zeros(M, D, device=self.device, dtype=torch.float32)   # gradient of the residual stream
+        # gradient of the residual stream (SAM: lp_f32_resid_out_bwd writes all of it)
+        dx = (torch.empty if pl.lnf is None else torch.zeros)(M, D, device=self.device, dtype=torch.float32)
         def scaled(j: int, nm: str) -> dict:
             """_ln_bwd's LayerScale arguments for the gradient that feeds branch ``nm`` ("1": attention, "2": MLP) of layer j; {} for the ViT"""
             if "ls1" not in pl.layers[j]:
                 return {}
             return dict(ls=pl.layers[j]["ls" + nm], branch=T[f"l{j}." + ("proj" if nm == "1" else "fc2")])
 
-        dcur = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, n_prefix=self.n_prefix,
-                            **scaled(pl.depth - 1, "2"))
+        if pl.lnf is None:   # SAM: the head's gradient starts the stream gradient and is the operand of the last fc2's backward
+            dcur = d_feat.view(M, D)
+            check(self._lib.lp_f32_resid_out_bwd(_p(dcur), M * D, _p(dx), ops._stream()), "lp_f32_resid_out_bwd")
+        else:
+            dcur = self._ln_bwd(d_feat, T["x_last"], T["mf"], T["rf"], pl.lnf, M, dx, drop_T=drop_T, want_bf16=True, n_prefix=self.n_prefix,
+                                **scaled(pl.depth - 1, "2"))
         rope_tab, rope_seq = T.get("rope_tab"), T.get("rope_seq")
         for i in range(pl.depth - 1, -1, -1):
             L = pl.layers[i]
@@ -179,10 +202,16 @@ class Fp32ViTEngine(Fp32Head, ViTEngine):
             d_y2 = self._linear_bwd(L["fc1"], t("y2"), d_h1, M)
             dcur = self._ln_bwd(d_y2, t("x_mid"), t("m2"), t("r2"), L["ln2"], M, dx, want_bf16=True, **scaled(i, "1"))
             d_attn = self._linear_bwd(L["proj"], t("attn"), dcur, M)
-            dqkv = self._f32(M, qs)
-            dS = self._f32(Bs * nh * Tn, Tn)
-            check(self._lib.lp_f32_attn_bwd(_p(t("qkv")), qs, D, 2 * D, _p(d_attn), D, _p(t("P")), Bs, nh, Tn, scale, _p(dS), _p(dqkv), qs,
+            ws = L.get("window", 0)
+            aB, aT = self.window_rows(B, gh, gw, ws) if ws else (Bs, Tn)
+            if ws:   # d_attn gathered into windows, pad rows zero
+                d_attn = self._win_part(d_attn, D, D, B, gh, gw, ws, None)
+            dqkv = self._f32(aB * aT, qs)
+            dS = self._f32(aB * nh * aT, aT)
+            check(self._lib.lp_f32_attn_bwd(_p(t("qkv")), qs, D, 2 * D, _p(d_attn), D, _p(t("P")), aB, nh, aT, scale, _p(dS), _p(dqkv), qs,
                                             ops._stream()), "lp_f32_attn_bwd")
+            if ws:   # scattered back; the pad rows' dK / dV summed into the qkv bias gradient
+                dqkv = self._win_unpart(dqkv, qs, B, gh, gw, ws, pad_colsum=self.G[L["qkv"].b_off:L["qkv"].b_off + qs])
             if trace is not None:
                 trace[f"l{i}.dqkv"] = dqkv
             if rope_tab is not None:   # the transposed rotation of dQ / dK, before the qkv weight gradient reads them

@@ -26,6 +26,9 @@ HOT = ("lp::conv_pipe_kernel", "lp::conv_spec_kernel", "lp::conv_wgrad_pipe_kern
        "lp::layernorm_ls_fwd_kernel", "lp::layernorm_ls_bwd_kernel",
        # the DINOv3 step: the rotation of q / k (24 launches per step) and the token assembly with registers
        "lp::rope_kernel", "lp::vit_reg_tokens_fwd_kernel", "lp::vit_reg_tokens_bwd_kernel",
+       # the SAM step: the window moves (32 launches per step), the prefix-free token assembly and the last residual add
+       "lp::window_partition_kernel", "lp::window_unpartition_kernel", "lp::vit_pos_tokens_fwd_kernel", "lp::vit_pos_tokens_bwd_kernel",
+       "lp::resid_out_fwd_kernel", "lp::resid_out_bwd_kernel",
        # crop-zoom prediction: the per-frame crop + resize (one launch per window of the second pass) and the two box kernels around it
        "lp::frames_crop_resize_kernel", "lp::bbox_from_keypoints_kernel", "lp::bbox_smooth_kernel")
 # decode_bwd_kernel<R, TY, NE = 64, ...> is the catch-all instantiation for maps larger than any BASELINE config selects (ne > 18 elements per
